@@ -1,6 +1,7 @@
 """Benchmark of the message-passing hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]      (N > 1: this process starts N rank processes itself)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+                                                             (N > 1: this process starts N rank processes itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W      (the launcher starts them)
 
@@ -14,13 +15,16 @@ run BASELINE configs[1] (chain of 1000 cliques of 64^3 doubles) and configs[2] (
 MRF of cardinality 8, junction tree by this repo's own builder) in the same format.
 
 Prints ONE JSON line on rank 0.  `value` = algorithmic clique-potential GB/s of the whole
-job (SURVEY.md 8d definition of algorithmic bytes), `messages_per_sec` beside it.
-`roofline` is for the dominant kernel (config 4: jt_propagate_flow, both phases of the propagate
+job (SURVEY.md 8d definition of algorithmic bytes), `messages_per_sec` beside it, `ms_per_step` = wall time of
+one timed step.  A plain run does only what that line needs: set-up, W warm-up steps, the K timed steps, the
+line.  `--dump-outputs DIR` then writes what the last timed step computed (dump_outputs).  Everything else
+runs with `--full` only: the parity checks, the CPU baselines, the sub-results below and `roofline`.
+With `--full`, `roofline` is for the dominant kernel (config 4: jt_propagate_flow, both phases of the propagate
 in one dataflow launch; configs 2 and 3: jt_distribute_flow[_chain], the whole distribute phase in
 one launch), timed with hipEvents on the plan's own stream: ONE event before the first timed step and
 ONE after the last (no event between the steps: an event costs 2-3 us of idle GPU), divided by the
 steps; where a step is two launches, the kernel's share of it comes from a few propagates timed after
-the timed region.  With the default workload on one GPU the line also carries `configs`: one measured
+the timed region.  With `--full` and the default workload on one GPU the line also carries `configs`: one measured
 sub-result per other BASELINE config (c2, c3, c3_api_end_to_end, c5_multiset64), each with
 `ms_per_step`, algorithmic bytes, roofline fraction and a parity flag.  `cpu_baseline` times the numpy restatement of the
 reference's einsum sequence (oracle/jt_oracle.py: beliefs_refshaped) on one host core over a
@@ -62,8 +66,8 @@ def multiset_roofline(stats, ms, alg_bytes):
             "pipe_occupancy_note": "float64 vector instructions (a multiplication holds the pipe as long as a fused multiply-add) / %.1f T lane instructions/s measured" % F64_PEAK_TINSTS,
             "hbm": {"algorithmic_bytes_per_step": alg_bytes, "GBps": alg_bytes / (ms * 1e-3) / 1e9, "frac": alg_bytes / (ms * 1e-3) / 1e9 / HBM_PEAK_GBPS,
                     "traffic": None, "traffic_source": "profiles/ (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of bench.py --batch 64 --multiset)"}}
-TRAFFIC_FILE = os.path.join("profiles", "r06_hbm_traffic.json")
-TRAFFIC_CASES_FILE = os.path.join("profiles", "r06_hbm_traffic_cases.json")
+TRAFFIC_FILE = os.path.join("profiles", "r07_hbm_traffic.json")
+TRAFFIC_CASES_FILE = os.path.join("profiles", "r07_hbm_traffic_cases.json")
 
 
 def case_traffic(case, source_id):
@@ -562,6 +566,35 @@ def sub_configs(device, spec_c4, source_id, single_ms):
     return out
 
 
+DUMP_BYTES = 48 << 20          # --dump-outputs: at most this many bytes of beliefs in all (the sample stays under 64 MB)
+DUMP_SEED = 7
+
+
+def dump_outputs(plan, out_dir, dtype, n_sets):
+    """--dump-outputs DIR: what the last timed step computed, as its caller receives it - clique beliefs in the caller's axis
+    order, in the table's precision - for a fixed, seeded sample: at most four evidence sets (the first and the last among them)
+    and, per set, the cliques in a seeded order (the root clique first) that fit DUMP_BYTES / sets.  One file per belief,
+    DIR/belief_set<b>_clique<c>.npy.  Only cliques this process holds (a sharded run: rank 0's).  The potentials come from
+    fixed seeds, so the same arguments give the same files on every build."""
+    import numpy as np
+    rng = np.random.default_rng(DUMP_SEED)
+    sets = sorted({0, n_sets - 1} | {int(b) for b in rng.choice(n_sets, size=min(n_sets, 2), replace=False)})
+    cliques = [plan.root] + [int(c) for c in rng.permutation(plan.cliques) if c != plan.root]
+    itemsize = np.dtype(dtype).itemsize
+    os.makedirs(out_dir, exist_ok=True)
+    written = 0
+    for b in sets:
+        room = DUMP_BYTES // len(sets)
+        for c in cliques:
+            nbytes = int(np.prod(plan.node_shape[c], dtype=np.int64)) * itemsize
+            if plan.owns(c) and nbytes <= room:
+                np.save(os.path.join(out_dir, "belief_set%d_clique%d.npy" % (b, c)), plan.belief(c, batch=b, dtype=dtype))
+                room -= nbytes
+                written += 1
+    if not written:
+        raise SystemExit("--dump-outputs: no clique belief of this workload fits the %d MiB sample (%d MiB per evidence set)"
+                         % (DUMP_BYTES >> 20, (DUMP_BYTES // len(sets)) >> 20))
+
 
 def spawn_ranks(args, argv):
     """`python bench.py --gpus N` without a launcher: start the N rank processes from HERE - this process never loads
@@ -641,7 +674,7 @@ def main():
     ap.add_argument("--lattice-w", type=int, default=167, help="--config c3: lattice columns (6 rows)")
     ap.add_argument("--dtype", default="f32", choices=["f32", "f64"])
     ap.add_argument("--cpu-sample", type=int, default=-1,
-                    help="size of the CPU baseline's sample: cliques of the tree (c4: default 256 = the full workload, ~4-25 s "
+                    help="with --full: size of the CPU baseline's sample: cliques of the tree (c4: default 256 = the full workload, ~4-25 s "
                          "on one core; c2: default 100 of the 1000 cliques) or lattice columns (c3: default 60); 0 = skip (and skip the sub-results "
                          "for the other configs: measurement tools run the headline workload alone)")
     ap.add_argument("--cpu-all-cores", action="store_true",
@@ -659,10 +692,17 @@ def main():
                     help="create this many other (small, idle) device plans first: A/B for the launch-order rule - an idle "
                          "plan must not cost the benchmark plan its blockIdx-order launches")
     ap.add_argument("--no-configs", action="store_true",
-                    help="skip the sub-results for the other BASELINE configs (c2, c3, c3 API call, c5 multi-set) that the default "
-                         "one-GPU run adds to its line")
+                    help="skip the sub-results for the other BASELINE configs (c2, c3, c3 API call, c5 multi-set) that --full "
+                         "adds to the line of the default one-GPU run")
     ap.add_argument("--spawn-timeout", type=int, default=900, help="seconds the self-started rank processes may take")
+    ap.add_argument("--full", action="store_true",
+                    help="also what the headline figure does not need: parity checks, CPU baselines, the sub-results for the other "
+                         "BASELINE configs, the roofline of the dominant kernel (propagates timed with events after the timed region)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write a fixed, seeded sample of the beliefs the last step computed to DIR/<name>.npy")
     args = ap.parse_args()
+    if (args.per_launch or args.cpu_all_cores) and not args.full:
+        raise SystemExit("--per-launch and --cpu-all-cores are parts of --full")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(spawn_ranks(args, sys.argv[1:]))
@@ -826,10 +866,12 @@ def main():
     plan.sync()
     barrier()
     elapsed = rdzv.allreduce_max(time.perf_counter() - t0)      # max over ranks
+    if args.dump_outputs and rank == 0:
+        dump_outputs(plan, args.dump_outputs, np.float32 if args.dtype == "f32" else np.float64, args.batch)
     # How a step divides over its launches (plans of two launches: collect, distribute; per level with --per-launch): from a
     # few propagates timed with events AFTER the timed region - the events cost 2-3 us of idle GPU each, which is why they
     # are not in it.
-    if not args.no_profile:
+    if args.full and not args.no_profile:
         n_prof = 8
         plan.set_profiling(n_prof, per_launch=args.per_launch or args.split_variants, stride=1)
         for _ in range(n_prof):
@@ -840,7 +882,9 @@ def main():
     z = plan.z() if plan.owns(plan.root) else None
     belief_dev = None
     rccl_info = per_rank_ms = None
-    if world > 1:
+    if world > 1 and not replicas:                   # the rank holding the root clique knows Z: share it
+        z = rdzv.allreduce_max(z if z is not None else -1.0e300)
+    if args.full and world > 1:
         # what RCCL itself says about the communicator, and every rank's own step time, gathered on rank 0
         import ctypes as C2
         nr, ur, cd = C2.c_int32(-1), C2.c_int32(-1), C2.c_int32(-1)
@@ -850,13 +894,12 @@ def main():
         recs = [json.loads(x.decode()) for x in rdzv.allgather(mine_rec)]
         rccl_info = {"ncclCommCount": sorted({r["ncclCommCount"] for r in recs}), "ranks": [{k: r[k] for k in ("rank", "device", "ncclCommUserRank", "ncclCommCuDevice")} for r in recs]}
         per_rank_ms = [r["ms_per_step"] for r in recs]
-    if replicas:
+    if args.full and replicas:
         # replicas: every rank checks its own first evidence set (a marginal sums to that set's Z), the worst goes into the line
         m = plan.marginals([(n - 1, [spec["node_vars"][n - 1][0]])], batch=0)[0]
         belief_dev = rdzv.allreduce_max(abs(float(m.sum()) - z) / abs(z))
-    elif world > 1:                                  # the rank holding the root clique knows Z: share it
-        z = rdzv.allreduce_max(z if z is not None else -1.0e300)
-        # ... and every rank checks the DISTRIBUTE side of the sharded run on cliques of its own (Z only proves the
+    elif args.full and world > 1:
+        # every rank checks the DISTRIBUTE side of the sharded run on cliques of its own (Z only proves the
         # collect side): a clique belief sums to Z whatever the clique.  First, middle and last clique a rank owns, one
         # single-variable marginal each (formed on the device); the worst relative deviation over all ranks goes
         # into the line.
@@ -908,7 +951,7 @@ def main():
                 "idle_plans": args.idle_plans, "Z": z, "library": version,
             },
         }
-        if not args.no_profile and stats["kernels"]:
+        if args.full and not args.no_profile and stats["kernels"]:
             name, k = max(stats["kernels"].items(), key=lambda kv: kv[1]["ms"])
             per_launch_bytes = k["bytes"] / k["launches"]          # (profiled: evidence set 0 only)
             # the kernel's share of a step, from the evented propagates after the timed region; its time = that share of
@@ -960,7 +1003,7 @@ def main():
                 out["roofline"]["collect_ms"] = out["roofline"]["distribute_ms"] = None
                 out["roofline"]["phases_in_one_launch"] = True
         cpu_n = args.cpu_sample if args.cpu_sample >= 0 else {"c4": n, "c2": 100, "c3": 60}[args.config]
-        if cpu_n > 0 and world == 1:
+        if args.full and cpu_n > 0 and world == 1:
             if args.config == "c4":
                 sample = synthetic.wide_binary_tree(n_cliques=cpu_n, width=args.width, sep=args.sep, card=args.card, seed=0)
                 out["cpu_baseline"] = cpu_baseline(sample, 4, "%d-clique balanced binary tree, same clique shape (width %d, card %d, %d shared)%s"
@@ -977,23 +1020,24 @@ def main():
                 out["cpu_baseline_all_cores"] = all_cores
         default_c4 = (args.config == "c4" and args.cliques == 256 and args.width == 20 and args.sep == 10
                       and args.card == 2 and args.dtype == "f32" and not (args.share or args.multiset))
-        if default_c4 and z is not None:
+        if args.full and default_c4 and z is not None:
             # Z of the default workload as one GPU and the numpy oracle compute it: a sharded run must agree
             out["config"]["Z_expected"] = Z_DEFAULT_C4
             out["config"]["Z_rel_err"] = abs(z - Z_DEFAULT_C4) / Z_DEFAULT_C4
-        if world > 1:
+        if args.full and world > 1:
             out["config"]["rccl"] = rccl_info
             out["config"]["ms_per_step_per_rank"] = per_rank_ms
+            # (replicas - every rank: a marginal of its first evidence set vs that set's Z; sharded - three cliques per rank: sum of
+            #  the belief vs Z)
+            out["config"]["replica_marginal_sums_rel_err" if replicas else "sharded_belief_sums_rel_err"] = belief_dev
         if replicas:
-            out["config"]["replica_marginal_sums_rel_err"] = belief_dev       # (every rank: a marginal of its first evidence set vs that set's Z)
-            out["config"]["multi_gpu_note"] = "replicas only: RCCL is initialised (the communicator's size is in config.rccl) and carries no data"
+            out["config"]["multi_gpu_note"] = "replicas only: RCCL is initialised (with --full, the communicator's size is in config.rccl) and carries no data"
         elif world > 1:
-            out["config"]["sharded_belief_sums_rel_err"] = belief_dev      # (three cliques per rank: sum of the belief vs Z)
             out["config"]["multi_gpu_note"] = ("transport: %s" % os.environ["JTP_RCCL_LIB"] if os.environ.get("JTP_RCCL_LIB")
                                                else "transport: RCCL (librccl.so.1), ncclSend/ncclRecv grouped per cut level")
         if args.share or args.multiset:
             out["config"]["Z_note"] = "Z is evidence set 0's P(evidence) * Z; parity of evidence runs: tests/test_gpu_configs.py"
-        if lattice is not None:
+        if args.full and lattice is not None:
             # size-independent checks in the line: every factor marginal sums to Z; the single-variable marginals that
             # different factors imply agree (calibration across the whole tree)
             tree = lattice["tree"]
@@ -1011,6 +1055,7 @@ def main():
             out["parity"] = {"factor_marginals_sum_to_Z_rel_err": float(np.max(np.abs(sums - z)) / z),
                              "calibration_rel_err": worst, "tolerance": 5e-6,
                              "ok": bool(np.max(np.abs(sums - z)) <= 5e-6 * z and worst < 5e-6)}
+        if lattice is not None:
             out["config"]["junction_tree_build_s"] = lattice["t_build"]
             out["config"]["bytes_definition"] = ("covered-shape potentials + messages, no belief tables (what the reference's evaluate / propagate leave, "
                                                  "junctiontree.py:52-61, 264-274)" if plan.cover is not None else "SURVEY.md 8d: every clique at its full shape")
@@ -1018,7 +1063,7 @@ def main():
                                            "frac": lattice["alg_full"] * args.steps / elapsed / 1e9 / HBM_PEAK_GBPS,
                                            "definition": "SURVEY.md 8d to the letter: every clique at its full shape, read in both passes, belief written"}
             out["config"]["cliques_without_table"] = lattice["stats"]["n_unit_cliques"]
-        run_subs = (default_c4 and world == 1 and args.batch == 1 and not args.no_configs and args.cpu_sample != 0 and not args.level_launches
+        run_subs = (args.full and default_c4 and world == 1 and args.batch == 1 and not args.no_configs and args.cpu_sample != 0 and not args.level_launches
                     and not args.split_variants and not args.per_launch and args.idle_plans == 0
                     and args.block_log2 == 0 and args.lds_budget == 0 and args.layout_policy == 0)
         if run_subs:

@@ -13,7 +13,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "junctiontree_amd", "lib")
 LIB = os.path.join(LIBDIR, "libjtprop.so")
-INST = ["jtp_inst_%s_%s.hip" % (fam, t) for fam in ("multi", "mix", "mixc", "both", "flow", "level", "shape") for t in ("f32", "f64")]
+# (longest compile first: a worker that frees up takes the next unit in this order, so the short ones fill in at the end)
+INST = ["jtp_inst_%s_%s.hip" % (fam, t) for fam in ("both", "bothm", "level", "mixc", "mix", "flow", "multi", "shape") for t in ("f32", "f64")]
 SOURCES = ["jtp_plan.cpp", "jtp_engine.hip"] + INST       # (compiled in parallel, one object each, then linked)
 DEPS = SOURCES + ["jtp_internal.h", "jtp_plan.h", "jtp_kernels.hip.h", os.path.join("..", "..", "include", "jtprop.h")]
 
@@ -66,7 +67,7 @@ def build(force=False, verbose=True, extra=(), out=None, jobs=None):
              '-DJTP_SOURCE_ID="%s"' % sid] + list(extra)
     objdir = tempfile.mkdtemp(prefix="jtprop_build_")
     # objects of translation units whose sources did not change are taken from a cache beside the library (git-ignored):
-    # a planner-only change recompiles jtp_plan.cpp and the engine, not the twelve kernel instantiation units
+    # a planner-only change recompiles jtp_plan.cpp and the engine, not the kernel instantiation units
     cache = os.path.join(LIBDIR, "objcache")
     os.makedirs(cache, exist_ok=True)
     import hashlib
@@ -107,7 +108,7 @@ def build(force=False, verbose=True, extra=(), out=None, jobs=None):
             return obj
         # (the template translation units take 1-2 GiB of compiler each: at most eight at once, JTP_BUILD_JOBS overrides)
         jobs = jobs or int(os.environ.get("JTP_BUILD_JOBS", 0)) or max(1, min(len(SOURCES), os.cpu_count() or 2, 8))
-        with ThreadPoolExecutor(jobs) as pool:          # (the heaviest translation units are listed first)
+        with ThreadPoolExecutor(jobs) as pool:
             objs = list(pool.map(compile_one, INST + ["jtp_engine.hip", "jtp_plan.cpp"]))
         # link beside the target and move the result into place: a process that has the old library mapped keeps it,
         # nobody ever sees a half-written one

@@ -1,4 +1,4 @@
 // One message-passing kernel for one storage type, compiled on its own (jtp_kernels.hip.h, "Explicit instantiation lists").
 #define JT_INST_TU
 #include "jtp_kernels.hip.h"
-JT_INST_PROPAGATE(, float)
+JT_INST_PROPAGATE_MARG(, float)

@@ -3097,7 +3097,11 @@ __global__ __launch_bounds__(256) void jt_marg_unpack(const JtMargDesc *__restri
     X template __global__ void jt_distribute<T, 1, 2>(JT_KARGS(T));          \
     X template __global__ void jt_distribute<T, 1, 3>(JT_KARGS(T));
 #define JT_INST_MULTI(X, T) X template __global__ void jt_multi_flow<T>(JT_KARGS(T));
-#define JT_INST_BOTH(X, T) X template __global__ void jt_propagate_flow<T>(JT_KARGS(T)); X template __global__ void jt_propagate_flow_marg<T>(JT_KARGS(T));
+// (the two kernels of a propagate in one launch are the largest of all - together 20 minutes of one compiler - so each has a
+//  translation unit of its own: jtp_inst_both_*.hip and jtp_inst_bothm_*.hip)
+#define JT_INST_BOTH(X, T) JT_INST_PROPAGATE(X, T) JT_INST_PROPAGATE_MARG(X, T)
+#define JT_INST_PROPAGATE(X, T) X template __global__ void jt_propagate_flow<T>(JT_KARGS(T));
+#define JT_INST_PROPAGATE_MARG(X, T) X template __global__ void jt_propagate_flow_marg<T>(JT_KARGS(T));
 #define JT_INST_MIX_V(X, T, V)                                                  \
     X template __global__ void jt_collect_level_mix<T, V>(JT_KARGS(T));         \
     X template __global__ void jt_distribute_level_mix<T, V>(JT_KARGS(T));      \

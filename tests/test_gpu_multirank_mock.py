@@ -157,7 +157,7 @@ def test_bench_starts_its_own_ranks(gpus):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["JTP_RCCL_LIB"] = _build_mock()
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "5", "--warmup", "2",
-                          "--cpu-sample", "0"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+                          "--cpu-sample", "0", "--full"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
     assert res.returncode == 0, res.stderr.decode()[-2000:]
     lines = [ln for ln in res.stdout.decode().splitlines() if ln.startswith("{")]
     assert len(lines) == 1, res.stdout.decode()
@@ -180,7 +180,7 @@ def test_bench_replicas_of_evidence_sets_over_two_ranks(flag):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["JTP_RCCL_LIB"] = _build_mock()
     res = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--cpu-sample", "0",
-                          "--batch", "8", flag, "--cliques", "63", "--width", "16", "--sep", "8"], env=env, stdout=subprocess.PIPE,
+                          "--full", "--batch", "8", flag, "--cliques", "63", "--width", "16", "--sep", "8"], env=env, stdout=subprocess.PIPE,
                          stderr=subprocess.PIPE, timeout=600)
     assert res.returncode == 0, res.stderr.decode()[-2000:]
     lines = [ln for ln in res.stdout.decode().splitlines() if ln.startswith("{")]

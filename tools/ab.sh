@@ -8,8 +8,8 @@ mkdir -p $OUT
 L=junction-tree_amd/junctiontree_amd/lib
 for i in $(seq $REPS); do
   for n in "$@"; do
-    if [ "$n" = cur ]; then env -u JTPROP_LIB python bench.py $ARGS --cpu-sample 0 > $OUT/${n}_$i.json 2>&1
-    else JTPROP_LIB=$L/libjtprop_$n.so python bench.py $ARGS --cpu-sample 0 > $OUT/${n}_$i.json 2>&1; fi
+    if [ "$n" = cur ]; then env -u JTPROP_LIB python bench.py --full $ARGS --cpu-sample 0 > $OUT/${n}_$i.json 2>&1
+    else JTPROP_LIB=$L/libjtprop_$n.so python bench.py --full $ARGS --cpu-sample 0 > $OUT/${n}_$i.json 2>&1; fi
   done
 done
 python tools/bsum.py $OUT/*.json | grep "ms/step\|unread"

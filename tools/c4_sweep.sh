@@ -5,7 +5,7 @@ OUT=${1:-gpurun_out/c4sweep.txt}
 MODE=${2:-consts}
 : > $OUT
 run() {
-    env $1 timeout -k 10 100 python3 bench.py --cpu-sample 0 --steps 100 > /tmp/c4s.json 2>/dev/null || exit 1
+    env $1 timeout -k 10 100 python3 bench.py --full --cpu-sample 0 --steps 100 > /tmp/c4s.json 2>/dev/null || exit 1
     echo "$1 : $(python3 tools/bsum.py /tmp/c4s.json | tr '\n' ' ' | tr -s ' ')" >> $OUT
 }
 if [ "$MODE" = consts ]; then

@@ -9,7 +9,7 @@
 export TMPDIR=/tmp
 OUT=$PWD/gpurun_out/prof
 rm -rf $OUT; mkdir -p $OUT
-B="python3 bench.py"
+B="python3 bench.py --full"
 L=junction-tree_amd/junctiontree_amd/lib
 ID="# library build: $(cat $L/BUILD_ID 2>/dev/null | tr '\n' ' ')"
 hdr() { echo "$ID" > $1; }          # start a text file with the build id
@@ -48,7 +48,7 @@ if [ -f $L/libjtprop_stamps.so ]; then
   unset JTPROP_LIB JTP_DEBUG
 fi
 echo "benches done" > $OUT/progress.txt
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o kt -- python3 bench.py --steps 20 --warmup 3 --cpu-sample 0 > $OUT/kt_bench.json 2> $OUT/kt.err
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt -o kt -- python3 bench.py --full --steps 20 --warmup 3 --cpu-sample 0 > $OUT/kt_bench.json 2> $OUT/kt.err
 # ... and of the whole API call on config 3 (jt_eval_batch, the message-passing kernels, jt_marginals)
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/kt_c3api -o kt -- python3 tools/run_c3.py > $OUT/kt_c3api.txt 2> $OUT/kt_c3api.err
 echo "kernel trace done" >> $OUT/progress.txt

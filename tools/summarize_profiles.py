@@ -31,7 +31,7 @@ def rows(pattern):
 stats = [r for r in rows("kt/**/*kernel_stats.csv") if "jt_" in r.get("Name", "")]
 if stats:
     with open(os.path.join(dst, "kernel_stats.csv"), "w", newline="") as fh:
-        fh.write("# library build: %s git %s (rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 20 --warmup 3 --cpu-sample 0)\n" % (source_id, git_head))
+        fh.write("# library build: %s git %s (rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 20 --warmup 3 --cpu-sample 0)\n" % (source_id, git_head))
         w = csv.DictWriter(fh, fieldnames=list(stats[0].keys()))
         w.writeheader()
         w.writerows(stats)
