@@ -61,6 +61,14 @@ extern "C" {
 #define JTP_NO_COMPACT 128u /* store every clique table padded to powers of two in every variable (round-1 layout).  By
                                default the rows above the thread part are stored at the true cardinalities         */
 
+#define JTP_SCALED 256u     /* overflow-safe propagate: every message is divided by a power of two right after it is produced
+                               (its largest entry then lies in [1, 2)), the exponents are kept per evidence set, and the
+                               read-out reports them: jtp_get_log2_scale, jtp_get_log_z.  Powers of two commute exactly with
+                               every multiply and add downstream, so - absent underflow, overflow and subnormals - a scaled
+                               propagate gives the unscaled tables bit for bit, up to a known exponent per node.  Such a plan
+                               always launches per tree level (as JTP_LEVEL_LAUNCHES) with one small launch per level and phase
+                               on top; refused (JTP_EUNSUPPORTED) with JTP_MULTISET and with n_ranks > 1                    */
+
 typedef struct jtp_plan jtp_plan;
 
 /* Structure of one junction tree.  Mirrors the reference's data model
@@ -257,8 +265,17 @@ int jtp_get_marginals(jtp_plan *plan, int32_t batch, int32_t n, const int32_t *c
                       double *host);
 
 /* Z = sum of the root belief (the value the reference computes and drops,
- * computation.py:90-96). */
+ * computation.py:90-96).  On a JTP_SCALED plan: ldexp(sum of the scaled root belief, E_root) - which may be inf or 0 where
+ * Z lies outside float64; jtp_get_log_z always has it. */
 int jtp_get_z(jtp_plan *plan, int32_t batch, double *z);
+
+/* JTP_SCALED plans: every table the read-out returns for `node` (clique or separator: jtp_get_belief, jtp_get_marginal(s)) of the
+ * last propagate of evidence set `batch` is the true table times 2^-E; *e = E.  0 on plans without the flag. */
+int jtp_get_log2_scale(jtp_plan *plan, int32_t batch, int32_t node, int64_t *e);
+
+/* log|Z| = log|sum of the root belief| + E_root ln 2, and the sign of Z in {-1, 0, 1} (the reference allows signed values;
+ * sign 0: *log_abs_z = -inf).  Works on every plan (E = 0 without JTP_SCALED). */
+int jtp_get_log_z(jtp_plan *plan, int32_t batch, double *log_abs_z, int32_t *sign);
 
 /* ---- instrumentation ------------------------------------------------------------------ */
 

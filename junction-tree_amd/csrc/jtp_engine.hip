@@ -10,6 +10,7 @@
 #include <unistd.h>
 
 #include <cerrno>
+#include <cmath>
 
 #include <algorithm>
 #include <atomic>
@@ -223,6 +224,12 @@ struct BatchBuffers {
     bool ev_any = false;            // ... and it observes something: the kernels get a null table otherwise (single-set plans: the lean
                                     // unit pass takes that for "no evidence anywhere", jt_unit_collect)
     uint32_t *sync = nullptr;       // dataflow launches: abort flag and ticket counters
+    // JTP_SCALED plans: log2 of the power of two every message of the last propagate was divided by (slot 2 * psep: upward,
+    // + 1: downward), rewritten by every propagate (jt_rescale_level); on the host, once a read-out asks: the exponent E of
+    // every planner node and separator - what the device holds for it is the true table x 2^-E (fetch_scale)
+    int32_t *exps = nullptr;
+    bool scale_fresh = false;
+    std::vector<int64_t> node_e, sep_e;
     uint32_t epoch = 0;             // propagates enqueued so far; its parity selects the message arena half
     uint32_t flow_runs = 0;         // of which dataflow
     uint32_t ticket_runs = 0;       // of which in ticket order: the segments' ticket counters only grow, by one launch's workgroups
@@ -333,6 +340,7 @@ struct jtp_plan {
     JtTask *d_tasks = nullptr;
     JtBlock *d_blocks = nullptr;
     JtBlock *d_init[2] = {nullptr, nullptr};      // HostPlan::init_blocks on the device (mixed-radix plans)
+    JtRescale *d_rescale = nullptr;               // HostPlan::rescale on the device (JTP_SCALED plans)
     int *d_itab = nullptr;
     void *stage = nullptr;          // device staging buffer for host<->device conversion
     size_t stage_bytes = 0;
@@ -518,7 +526,7 @@ const char *jtp_last_error(void) { return g_err.c_str(); }
 #ifndef JTP_SOURCE_ID
 #define JTP_SOURCE_ID "unknown"
 #endif
-const char *jtp_version(void) { return "jtprop 0.6.0 (gfx950, HIP, RCCL p2p) src:" JTP_SOURCE_ID; }
+const char *jtp_version(void) { return "jtprop 0.7.0 (gfx950, HIP, RCCL p2p) src:" JTP_SOURCE_ID; }
 
 int jtp_host_alloc(void **ptr, size_t bytes) {
     if (!ptr) return set_err(JTP_EINVAL, "null argument");
@@ -595,6 +603,7 @@ void jtp_plan_destroy(jtp_plan *pl) {
             if (b.fix && (&b == &pl->bufs[0] || b.fix != pl->bufs[0].fix)) (void)hipFree(b.fix);
             if (b.ev) (void)hipFree(b.ev);
             if (b.sync) (void)hipFree(b.sync);
+            if (b.exps) (void)hipFree(b.exps);
         }
         if (pl->host_abort) (void)hipHostFree(pl->host_abort);
         for (auto &bt : pl->belief_tasks) {
@@ -610,6 +619,7 @@ void jtp_plan_destroy(jtp_plan *pl) {
         if (pl->d_blocks) (void)hipFree(pl->d_blocks);
         for (int m = 0; m < 2; ++m)
             if (pl->d_init[m]) (void)hipFree(pl->d_init[m]);
+        if (pl->d_rescale) (void)hipFree(pl->d_rescale);
         if (pl->d_itab) (void)hipFree(pl->d_itab);
         if (pl->stage) (void)hipFree(pl->stage);
         for (int i = 0; i < 2; ++i) {
@@ -813,6 +823,11 @@ int jtp_plan_create(const jtp_tree_desc *desc, jtp_plan **out) {
         CREATE_TRY(hipMemsetD32Async((hipDeviceptr_t)b.msg, (int)(uint32_t)(JT_UNWRITTEN & 0xffffffffu), mbytes / 4, pl->streams[0]));
         CREATE_TRY(hipMalloc((void **)&b.sync, (size_t)hp.sync_words * 4));
         CREATE_TRY(hipMemsetAsync(b.sync, 0, (size_t)hp.sync_words * 4, pl->streams[0]));
+        if (hp.scaled) {
+            const size_t ebytes = std::max<size_t>(2 * hp.ps.size(), 1) * sizeof(int32_t);
+            CREATE_TRY(hipMalloc((void **)&b.exps, ebytes));
+            CREATE_TRY(hipMemsetAsync(b.exps, 0, ebytes, pl->streams[0]));
+        }
     }
     CREATE_TRY(hipHostMalloc((void **)&pl->host_abort, 64, hipHostMallocMapped));
     *pl->host_abort = 0;
@@ -843,6 +858,10 @@ int jtp_plan_create(const jtp_tree_desc *desc, jtp_plan **out) {
     if (!hp.itab.empty()) {
         CREATE_TRY(hipMalloc((void **)&pl->d_itab, hp.itab.size() * sizeof(int32_t)));
         CREATE_TRY(hipMemcpy(pl->d_itab, hp.itab.data(), hp.itab.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    }
+    if (!hp.rescale.empty()) {
+        CREATE_TRY(hipMalloc((void **)&pl->d_rescale, hp.rescale.size() * sizeof(JtRescale)));
+        CREATE_TRY(hipMemcpy(pl->d_rescale, hp.rescale.data(), hp.rescale.size() * sizeof(JtRescale), hipMemcpyHostToDevice));
     }
     for (int m = 0; m < 2; ++m)
         if (!hp.init_blocks[m].empty()) {
@@ -1258,6 +1277,58 @@ __global__ __launch_bounds__(256) void jt_zero_copies(const JtTask *__restrict__
             msg[at + idx] = 0.0;
         }
     }
+}
+
+// JTP_SCALED plans: the messages one tree level has just produced are divided by a power of two each, in place, before the next
+// level reads them.  One workgroup per record (JtRescale: every copy of one message as its consumers read it), one launch per
+// kind-2 step.  Pass 1 takes the largest biased exponent field of the entries (an integer maximum: across the lanes of a row by
+// DPP row shifts, across rows by ds_bpermute, across the four waves through LDS); pass 2 multiplies every entry by 2^-e, e = that
+// field - 1023 clamped to [-1022, 1022] so that 2^-e is a normal double built from bits - the largest entry then lies in [1, 2)
+// (or [1, 4) after the clamp).  A field of 0 (all zero or subnormal) or 0x7ff (an inf or NaN somewhere) leaves the message as it
+// is, e = 0: a NaN then propagates exactly as on an unscaled plan.  Multiplying by a power of two is exact, zeros stay zeros.
+// (`msg`: the half of the evidence set's arena this propagate uses - 16-byte aligned; a record starts at any double.)
+__device__ __forceinline__ int jt_exp_field(double v) { return (__double2hiint(v) >> 20) & 0x7ff; }
+#define JT_ROW_DOWN_INT(v, N) __builtin_amdgcn_update_dpp(0, (v), 0x100 + (N), 0xf, 0xf, true)      // row_shl:N - lane + N of the row of 16, 0 beyond it
+
+__global__ __launch_bounds__(256) void jt_rescale_level(const JtRescale *__restrict__ recs, double *__restrict__ msg, int32_t *__restrict__ exps) {
+    __shared__ int wave_max[4];
+    const JtRescale r = recs[blockIdx.x];
+    const int tid = threadIdx.x;
+    double *p = msg + r.off;
+    // 16-byte vectors from the first even arena offset on; at most one entry before them and one behind
+    const int64_t head = ((r.off & 1) && r.count > 0) ? 1 : 0;
+    const int64_t npair = (r.count - head) >> 1;
+    const bool tail = ((r.count - head) & 1) != 0;
+    double2 *v = reinterpret_cast<double2 *>(p + head);
+    int mx = 0;
+    for (int64_t i = tid; i < npair; i += 256) {
+        const double2 x = v[i];
+        mx = max(mx, max(jt_exp_field(x.x), jt_exp_field(x.y)));
+    }
+    if (tid == 0 && head) mx = max(mx, jt_exp_field(p[0]));
+    if (tid == 1 && tail) mx = max(mx, jt_exp_field(p[r.count - 1]));
+    mx = max(mx, JT_ROW_DOWN_INT(mx, 1));
+    mx = max(mx, JT_ROW_DOWN_INT(mx, 2));
+    mx = max(mx, JT_ROW_DOWN_INT(mx, 4));
+    mx = max(mx, JT_ROW_DOWN_INT(mx, 8));              // lane 0 of every row of 16: the row's maximum
+    mx = max(mx, __shfl_xor(mx, 16, 64));
+    mx = max(mx, __shfl_xor(mx, 32, 64));              // lane 0: the wave's
+    if ((tid & 63) == 0) wave_max[tid >> 6] = mx;
+    __syncthreads();
+    const int field = max(max(wave_max[0], wave_max[1]), max(wave_max[2], wave_max[3]));
+    int e = 0;
+    if (field != 0 && field != 0x7ff) e = min(max(field - 1023, -1022), 1022);
+    if (tid == 0) exps[r.slot] = e;
+    if (e == 0) return;                                // (times 1: nothing to do)
+    const double scale = __hiloint2double((1023 - e) << 20, 0);
+    for (int64_t i = tid; i < npair; i += 256) {
+        double2 x = v[i];
+        x.x *= scale;
+        x.y *= scale;
+        v[i] = x;
+    }
+    if (tid == 0 && head) p[0] *= scale;
+    if (tid == 1 && tail) p[r.count - 1] *= scale;
 }
 
 // (`msg`, `nsets`: one evidence set's arena, or - multi-set plans - all of them, set_stride doubles apart; `halves`: bit h = arena half h)
@@ -1681,6 +1752,7 @@ int jtp_propagate(jtp_plan *pl, int32_t batch_begin, int32_t batch_end) {
         const bool flow = pl->flow && !per_launch;
         const int64_t half = std::max<int64_t>(hp.msg_doubles, 2);
         bb.epoch++;
+        bb.scale_fresh = false;
         JtFlow fl;
         memset(&fl, 0, sizeof fl);
         fl.sync = bb.sync;
@@ -1737,6 +1809,9 @@ int jtp_propagate(jtp_plan *pl, int32_t batch_begin, int32_t batch_end) {
                 fl.blk_base = (uint32_t)L.blk_off;
                 launch_variant(pl, L.variant, L.nblocks, L.lds_bytes, s, pl->d_tasks, pl->d_blocks + L.blk_off, pl->d_itab, bb.psi, bb.bel, bb.msg, fl);
                 if (per_launch) HIP_TRY(hipEventRecord(pl->ev[ev_base + 2 * st.first + 1], s));
+            } else if (st.kind == 2) {
+                // (JTP_SCALED: the messages the level before has just produced, a workgroup each)
+                hipLaunchKernelGGL(jt_rescale_level, dim3((unsigned)st.count), dim3(256), 0, s, pl->d_rescale + st.first, bb.msg + fl.cur_off, bb.exps);
             } else if (pl->fake_comm == 2) {
                 // loop-back: the step's sends and receives as one RCCL group addressed to this rank itself (RCCL pairs the k-th
                 // send to a peer with the k-th receive from it: a receive without a send of its own takes this rank's first
@@ -2221,11 +2296,96 @@ int jtp_get_marginals(jtp_plan *pl, int32_t batch, int32_t n, const int32_t *cli
     return check_flow(pl, batch);
 }
 
-int jtp_get_z(jtp_plan *pl, int32_t batch, double *z) {
+// sum of the root belief as the device holds it (a JTP_SCALED plan: Z x 2^-E_root)
+static int root_sum(jtp_plan *pl, int32_t batch, double *z) {
     if (!pl) return set_err(JTP_EINVAL, "null plan");
+    if (!z) return set_err(JTP_EINVAL, "null argument");
     if (pl->hp.pn[pl->hp.root].owner != pl->hp.rank && pl->hp.pn[pl->hp.root].owner != pl->hp.n_ranks)
         return set_err(JTP_EINVAL, "the root clique belongs to rank %d", pl->hp.pn[pl->hp.root].owner);
     return jtp_get_marginal(pl, batch, pl->hp.root, nullptr, 0, z);
+}
+
+// JTP_SCALED plans: the exponents of the last propagate of evidence set `batch`, and from them the exponent of every node - a walk
+// down the planner's own tree (re-rooted, virtual cliques included).  With U(c) = the sum of e_up over the subtree of c, the upward
+// message of c is the true one x 2^-U(c); the root multiplies all of them: E_root = sum of every e_up.  The downward message into c
+// carries what its parent's belief carries without c's own subtree, and its own exponent:
+//     E_child = E_parent - e_up(child) + e_dn(child);      separator (up x down) = E_parent + e_dn(child) = E_child + e_up(child).
+static int fetch_scale(jtp_plan *pl, int batch) {
+    HostPlan &hp = pl->hp;
+    BatchBuffers &b = pl->bufs[batch];
+    if (!hp.scaled || b.scale_fresh) return JTP_OK;
+    int rc = settle(pl, batch);
+    if (rc) return rc;
+    hipStream_t s = pl->streams[batch % pl->streams.size()];
+    std::vector<int32_t> ex(std::max<size_t>(2 * hp.ps.size(), 1), 0);
+    HIP_TRY(hipMemcpyAsync(ex.data(), b.exps, ex.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const int np = (int)hp.pn.size();
+    b.node_e.assign(np, 0);
+    b.sep_e.assign(hp.ps.size(), 0);
+    std::vector<int> order(np);
+    for (int c = 0; c < np; ++c) order[c] = c;
+    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return hp.pn[x].depth < hp.pn[y].depth; });
+    int64_t all_up = 0;
+    for (int c = 0; c < np; ++c)
+        if (hp.pn[c].psep >= 0) all_up += ex[2 * hp.pn[c].psep];
+    for (int c : order) {
+        const PNode &p = hp.pn[c];
+        if (p.psep < 0 || p.parent < 0) {
+            b.node_e[c] = all_up;
+            continue;
+        }
+        b.sep_e[p.psep] = b.node_e[p.parent] + ex[2 * p.psep + 1];
+        b.node_e[c] = b.sep_e[p.psep] - ex[2 * p.psep];
+    }
+    b.scale_fresh = true;
+    return JTP_OK;
+}
+
+int jtp_get_log2_scale(jtp_plan *pl, int32_t batch, int32_t node, int64_t *e) {
+    if (!pl || !e) return set_err(JTP_EINVAL, "null argument");
+    HostPlan &hp = pl->hp;
+    if (node < 0 || node >= hp.n_nodes) return set_err(JTP_EINVAL, "node %d out of range", node);
+    *e = 0;
+    if (!hp.scaled) return JTP_OK;
+    int rc = check_ready(pl, batch);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(hp.device));
+    rc = fetch_scale(pl, batch);
+    if (rc) return rc;
+    if (node < hp.n_cliques) *e = pl->bufs[batch].node_e[node];
+    else {
+        const int si = hp.sep_of_node[node];
+        if (si < 0) return set_err(JTP_EINVAL, "separator node %d is not part of the tree", node);
+        *e = pl->bufs[batch].sep_e[si];
+    }
+    return JTP_OK;
+}
+
+int jtp_get_z(jtp_plan *pl, int32_t batch, double *z) {
+    int rc = root_sum(pl, batch, z);
+    if (rc || !pl->hp.scaled) return rc;
+    rc = fetch_scale(pl, batch);
+    if (rc) return rc;
+    const int64_t e = pl->bufs[batch].node_e[pl->hp.root];
+    *z = ldexp(*z, (int)std::min<int64_t>(std::max<int64_t>(e, -100000), 100000));       // (inf or 0 where Z is outside float64)
+    return JTP_OK;
+}
+
+int jtp_get_log_z(jtp_plan *pl, int32_t batch, double *log_abs_z, int32_t *sign) {
+    if (!log_abs_z || !sign) return set_err(JTP_EINVAL, "null argument");
+    double sum = 0;
+    int rc = root_sum(pl, batch, &sum);
+    if (rc) return rc;
+    int64_t e = 0;
+    if (pl->hp.scaled) {
+        rc = fetch_scale(pl, batch);
+        if (rc) return rc;
+        e = pl->bufs[batch].node_e[pl->hp.root];
+    }
+    *sign = (sum > 0) - (sum < 0);                      // (a NaN sum: sign 0, log NaN)
+    *log_abs_z = log(fabs(sum)) + (e ? (double)e * 0.69314718055994530942 : 0.0);
+    return JTP_OK;
 }
 
 // ------------------------------------------------------------------------------------------ instrumentation
@@ -2289,6 +2449,7 @@ int jtp_get_stats(jtp_plan *pl, jtp_stats *st) {
     st->struct_size = (int32_t)sizeof(jtp_stats);
     const bool flow = pl->flow && !pl->prof_per_launch;
     st->n_launches = (int32_t)(flow ? hp.segments.size() : hp.launches.size());
+    for (const Step &sp : hp.steps) st->n_launches += sp.kind == 2 ? 1 : 0;      // (JTP_SCALED: the rescale launches between the levels)
     st->n_messages = hp.n_messages;
     st->n_tasks = (int32_t)hp.tasks.size();
     // multi-set plans: a table is read once per GROUP of evidence sets, messages once per set

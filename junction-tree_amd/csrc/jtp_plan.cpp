@@ -866,6 +866,12 @@ int PlanBuilder::read_description() {
     if (hp.knobs.layout_policy >= 0) hp.layout_policy = hp.knobs.layout_policy;               // experiments
     hp.compact = !hp.knobs.no_compact && !(d->flags & JTP_NO_COMPACT);
     hp.multiset = (d->flags & JTP_MULTISET) != 0;
+    hp.scaled = (d->flags & JTP_SCALED) != 0;
+    if (hp.scaled) {
+        if (hp.multiset) FAIL(JTP_EUNSUPPORTED, "JTP_SCALED with JTP_MULTISET: scaled multi-set plans are not built (share the potentials without JTP_MULTISET)");
+        if (d->n_ranks != 1) FAIL(JTP_EUNSUPPORTED, "JTP_SCALED with n_ranks = %d: scaled multi-rank plans are not built", d->n_ranks);
+        hp.flags |= JTP_LEVEL_LAUNCHES;            // the rescale steps sit between the levels: no dataflow launches
+    }
     if (hp.multiset) {
         if (d->n_ranks != 1) FAIL(JTP_EUNSUPPORTED, "multi-set plans run on one rank (evidence sets are independent: give every rank its own sets)");
         // Bit order: "epilogue first" (3) measured 2x faster than "traffic first" (2) on the width-20 tree (fewer
@@ -2408,6 +2414,33 @@ int PlanBuilder::schedule() {
         hp.launches.push_back(L);
         hp.steps.push_back(st);
     };
+    // JTP_SCALED: the messages one level has just produced (behind their reduce tasks) are divided by a power of two each
+    auto emit_rescale = [&](int phase, int level) {
+        if (!hp.scaled) return;
+        Step st;
+        st.kind = 2;
+        st.first = (int)hp.rescale.size();
+        auto add = [&](int psep, bool up) {
+            const PSep &s = hp.ps[psep];
+            JtRescale r;
+            r.off = up ? s.up_roff : s.dn_roff;
+            r.count = ((int64_t)1 << s.nbits) * (up ? s.up_rnpart : s.dn_rnpart);
+            r.slot = 2 * psep + (up ? 0 : 1);
+            r.pad = 0;
+            if (r.off >= 0) hp.rescale.push_back(r);
+        };
+        for (int c : by_level(level)) {
+            const PNode &p = hp.pn[c];
+            if (!mine(c)) continue;
+            if (phase == 0) {
+                if (p.psep >= 0) add(p.psep, true);
+            } else {
+                for (int k : p.children) add(hp.pn[k].psep, false);
+            }
+        }
+        st.count = (int)hp.rescale.size() - st.first;
+        if (st.count > 0) hp.steps.push_back(st);
+    };
     // Exchange order: ncclSend/ncclRecv (and every transport standing in for them) pair the operations
     // between two ranks in ISSUE order, so both sides of a cut must enumerate the cut edges of one level
     // in the same order whatever the numbering of the cliques: always by the CHILD clique of the edge
@@ -2430,6 +2463,7 @@ int PlanBuilder::schedule() {
         if (level >= 1) {
             emit_launches(0, level);
             emit_reduce(0, level);
+            emit_rescale(0, level);
         }
         for (int c : cut_children(level)) {                    // send what this level produced
             if (hp.pn[c].owner != hp.rank) continue;
@@ -2447,6 +2481,7 @@ int PlanBuilder::schedule() {
         }
         emit_launches(1, level);
         emit_reduce(1, level);
+        emit_rescale(1, level);
         for (int k : cut_children(level + 1)) {
             const int po = hp.pn[hp.pn[k].parent].owner;
             if (po == hp.rank && hp.pn[k].owner != hp.rank) comm_op(1, hp.pn[k].psep, 0, hp.pn[k].owner);
@@ -2459,6 +2494,7 @@ int PlanBuilder::schedule() {
 int PlanBuilder::finish() {
     // ---- dataflow schedule: runs of launches of one phase become one segment --------------------
     for (const Step &st : hp.steps) {
+        if (hp.scaled) break;                      // (a scaled plan launches per level: no segments, no flow steps)
         if (st.kind == 1) {
             hp.flow_steps.push_back(st);
             continue;
@@ -2862,6 +2898,15 @@ void jtp_plan_to_json(HostPlan &hp, bool with_tasks) {
           << ",\"off\":" << c.off << ",\"count\":" << c.count << "}";
     }
     o << "]";
+    if (hp.scaled) {                  // (plans without JTP_SCALED describe as they always did)
+        o << ",\"scaled\":1,\"rescale\":[";
+        for (size_t i = 0; i < hp.rescale.size(); ++i) {
+            const JtRescale &r = hp.rescale[i];
+            if (i) o << ",";
+            o << "{\"off\":" << r.off << ",\"count\":" << r.count << ",\"slot\":" << r.slot << "}";
+        }
+        o << "]";
+    }
     if (with_tasks) {
         o << ",\"tasks\":[";
         for (size_t t = 0; t < hp.tasks.size(); ++t) {

@@ -90,8 +90,19 @@ struct CommOp {
 };
 
 struct Step {
-    int kind = 0;                    // 0 launch, 1 comm group
-    int first = 0, count = 0;        // launch index, or [first, first+count) in comm
+    int kind = 0;                    // 0 launch, 1 comm group, 2 rescale (JTP_SCALED plans)
+    int first = 0, count = 0;        // launch index, or [first, first+count) in comm / in rescale
+};
+
+// JTP_SCALED plans: one record per (separator, direction) - the buffer consumers and the read-out read of that message (every
+// copy of it), divided by ONE power of two right after the level that produced it (kernel jt_rescale_level, a workgroup per
+// record); the exponent goes to slot `slot` (2 * psep + (downward ? 1 : 0)) of the evidence set's exponent array.  Read by the
+// kernel as it stands: 24 bytes.
+struct JtRescale {
+    int64_t off;                     // msg arena offset (doubles): PSep::*_roff
+    int64_t count;                   // doubles: copies x 2^nbits
+    int32_t slot;
+    int32_t pad;
 };
 
 // Dataflow schedule: consecutive launches of one phase run as ONE launch whose workgroups take
@@ -218,6 +229,8 @@ struct HostPlan {
     double alg_bytes_full = 0;           // algorithmic bytes with every clique counted at its full shape (SURVEY.md 8d to the letter)
     std::vector<CommOp> comm;
     std::vector<Step> steps;
+    std::vector<JtRescale> rescale;      // JTP_SCALED plans: the records of the kind-2 steps
+    bool scaled = false;                 // JTP_SCALED
     std::vector<Segment> segments;
     std::vector<Step> flow_steps;        // as `steps`, launches replaced by segments (kind 0: first = segment)
     int sync_words = 0;                  // uint32 words of the per-evidence-set sync buffer

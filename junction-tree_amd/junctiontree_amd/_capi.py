@@ -21,6 +21,7 @@ JTP_SHARE_POTENTIALS = 32
 JTP_FLOW_TICKETS = 16
 JTP_MULTISET = 64
 JTP_NO_COMPACT = 128
+JTP_SCALED = 256
 N_VARIANTS = 23
 MAX_VARS = 32            # variables per node the C ABI takes (JT_MAX_VARS); engine.Plan keeps one-state variables beyond that on the host
 
@@ -126,6 +127,8 @@ SYMBOLS = {
     "jtp_get_marginals": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32),
                                     C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_double)]),
     "jtp_get_z": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_double)]),
+    "jtp_get_log2_scale": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    "jtp_get_log_z": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
     "jtp_set_profiling": (C.c_int, [C.c_void_p, C.c_int32]),
     "jtp_set_profiling_granularity": (C.c_int, [C.c_void_p, C.c_int32]),
     "jtp_set_profiling_stride": (C.c_int, [C.c_void_p, C.c_int32]),

@@ -57,7 +57,8 @@ class Plan:
     def __init__(self, tree, node_vars, sizes, dtype="f64", device=0, n_batch=1,
                  n_ranks=1, rank=0, owner=None, plan_only=False, lds_budget=0, block_log2=0,
                  layout_policy=0, split_variants=False, keep_root=False, level_launches=False,
-                 flow_tickets=False, share_potentials=False, multiset=False, no_compact=False, root=None, cover=None, fold=None):
+                 flow_tickets=False, share_potentials=False, multiset=False, no_compact=False, root=None, cover=None, fold=None,
+                 scaled=False):
         self._lib = _capi.lib()
         self._handle = C.c_void_p()
         order, parent, parent_sep, children = flatten_tree(tree)
@@ -168,8 +169,12 @@ class Plan:
                    | (_capi.JTP_FLOW_TICKETS if flow_tickets else 0)
                    | (_capi.JTP_SHARE_POTENTIALS if share_potentials or multiset else 0)
                    | (_capi.JTP_MULTISET if multiset else 0)
-                   | (_capi.JTP_NO_COMPACT if no_compact else 0))
+                   | (_capi.JTP_NO_COMPACT if no_compact else 0)
+                   | (_capi.JTP_SCALED if scaled else 0))
         self.multiset = bool(multiset)
+        # `scaled` (JTP_SCALED): every message is divided by a power of two right after it is produced - no table of the propagate
+        # leaves floating-point range whatever Z is; `log_z`, `log2_scale` and `belief` / `marginals` (true table x 2^-log2_scale)
+        self.scaled = bool(scaled)
         d.lds_budget = lds_budget
         d.block_log2 = block_log2
         d.layout_policy = layout_policy
@@ -396,6 +401,20 @@ class Plan:
         val = C.c_double(0.0)
         _capi.check(self._lib.jtp_get_z(self._handle, batch, C.byref(val)))
         return val.value
+
+    def log_z(self, batch=0):
+        """(sign, log|Z|) of evidence set `batch`: Z = the sum of the root belief, with the exponents a scaled plan took out of
+        its messages put back in the logarithm - finite where `z()` would be inf or 0.  sign 0: Z == 0 (log|Z| = -inf)."""
+        val, sign = C.c_double(0.0), C.c_int32(0)
+        _capi.check(self._lib.jtp_get_log_z(self._handle, batch, C.byref(val), C.byref(sign)))
+        return int(sign.value), val.value
+
+    def log2_scale(self, node, batch=0):
+        """E of node `node` (clique or separator, caller's index): `belief(node)` and every marginal of it are the true table
+        times 2**-E.  0 on plans made without `scaled`."""
+        e = C.c_int64(0)
+        _capi.check(self._lib.jtp_get_log2_scale(self._handle, batch, self.abi_of[node], C.byref(e)))
+        return int(e.value)
 
     # ------------------------------------------------------------------ instrumentation
     def set_profiling(self, keep=1, per_launch=False, stride=1):

@@ -70,6 +70,15 @@ def einsum(xs, xs_keys, y_keys):
     return np.einsum(*call)
 
 
+def _normalised(tables):
+    """Every table divided by its own sum (a table that sums to zero - evidence of probability zero - stays as it is)."""
+    out = []
+    for t in tables:
+        total = t.sum()
+        out.append(t / total if total != 0 else t)
+    return out
+
+
 def _stage_changed_cliques(plan, ct, xs, changed=None):
     """`evaluate` on the device for the cliques whose member factors differ from what `plan` holds: one call into the
     library for all of them (`engine.Plan.stage_factors`).  Returns the number of cliques formed (`plan.staged_cliques`
@@ -183,7 +192,21 @@ class JunctionTree:
         self._memo["cover"] = ((hit[0] + 1) if hit is not None else 0, cover, [list(f) for f in ct.factor_graph.factors], list(ct.factor_to_maxclique))
         return cover
 
-    def plan(self, dtype="f64", trusted=False, fold=True):
+    # results of the last `propagate(..., normalize=True)` / `propagate_evidence_sets(..., normalize=True)`: log|Z| and the sign of Z
+    # (the reference allows signed values), one log|Z_e| per evidence set
+    @property
+    def log_z(self):
+        return self._memo.get("log_z")
+
+    @property
+    def z_sign(self):
+        return self._memo.get("z_sign")
+
+    @property
+    def log_z_sets(self):
+        return self._memo.get("log_z_sets")
+
+    def plan(self, dtype="f64", trusted=False, fold=True, scaled=False):
         """The device plan for the current variable sizes (sizes are read at call time, as
         `junctiontree.py:311` does: the reference's tests condition on evidence by setting
         a size to 1, `tests/test_junctiontree.py:393-411`)."""
@@ -194,7 +217,9 @@ class JunctionTree:
         # and a weak reference to the plan it was last given for (dtype, the sizes as they are NOW, its options, and the
         # factor structure its cover was computed from - by value: a recomputed cover may reuse the old list's id)
         sizes = self.clique_tree.factor_graph.sizes
-        memo = "plan" if fold else "plan_nofold"
+        # (`scaled`: the overflow-safe plan of `propagate(xs, normalize=True)` - an entry of its own, so that what the default call
+        #  trusts about "plan" is never said of another plan)
+        memo = ("plan" if fold else "plan_nofold") + ("_scaled" if scaled else "")
         hit = self._memo.get(memo)
         if trusted and hit is not None and hit[0][0] == dtype:      # (`propagate(xs, changed=...)`: sizes, options and factors are vouched for)
             plan = engine.cached_plan(hit[1], hit[2]())
@@ -211,25 +236,31 @@ class JunctionTree:
         #  without a table are formed inside the propagate's launch; fold=False: the plan `compute_beliefs` would make of this tree)
         ct = self.clique_tree
         extra = {"fold": (tuple(ct.factor_to_maxclique), tuple(map(tuple, ct.factor_graph.factors)))} if fold else {}
+        if scaled:
+            extra["scaled"] = True
         plan, key = engine.plan_for(self.tree, node_vars, sizes, dtype, return_key=True, cover=cover, **extra, **self._opts)
         self._memo[memo] = (mark, key, weakref.ref(plan))
         return plan
 
-    def propagate(self, xs, changed=None):
+    def propagate(self, xs, changed=None, normalize=False):
         """Belief propagation: factor values in, unnormalised factor marginals out (same
         list length and array shapes as `xs`; float64).
+
+        `normalize` (not in the reference, which has no overflow control): the propagate runs on an overflow-safe plan - every
+        message is divided by a power of two as it is produced, `engine.Plan(scaled=True)` - and every returned marginal is divided
+        by its own sum; `tree.log_z` is then log|Z| and `tree.z_sign` the sign of Z, finite where Z itself is beyond float64.
 
         `changed` (not in the reference; it answers the FIXME at `junctiontree.py:206-214`): the indices of the factors whose
         tables differ from the previous call on this tree, or "all".  By default every table is compared with what the device
         holds (one vectorised pass over all of them, so that arrays updated in place are seen); a caller that knows what it
         changed skips that - and vouches that the factor structure and every other table are what they were."""
         ct = self.clique_tree
-        trusted = changed is not None and "plan" in self._memo
+        trusted = changed is not None and ("plan_scaled" if normalize else "plan") in self._memo
         if trusted and "all_f32" in self._memo:          # (the caller vouches for the structure - shapes and dtypes with it)
             all_f32 = self._memo["all_f32"]
         else:
             all_f32 = self._memo["all_f32"] = all(type(x) is np.ndarray and x.dtype == np.float32 for x in xs)
-        plan = self.plan("f32" if all_f32 else "f64", trusted=trusted)
+        plan = self.plan("f32" if all_f32 else "f64", trusted=trusted, scaled=normalize)
         # evaluate (junctiontree.py:203-226) on the device: only factor tables cross PCIe, and only those of
         # cliques whose factors changed since this plan last saw them (the reference recomputes every clique on
         # every call and says so in a FIXME, junctiontree.py:206-214)
@@ -238,15 +269,23 @@ class JunctionTree:
         plan.propagate(sync=False)
         # marginalize (junctiontree.py:229-274) on the device: one launch for all factors, the factors of one clique
         # sharing the passes over its belief table
-        return plan.factor_marginals(ct.factor_graph.factors, ct.factor_to_maxclique, trusted=trusted)
+        out = plan.factor_marginals(ct.factor_graph.factors, ct.factor_to_maxclique, trusted=trusted)
+        if normalize:
+            self._memo["z_sign"], self._memo["log_z"] = plan.log_z()
+            out = _normalised(out)
+        return out
 
-    def propagate_evidence_sets(self, xs, evidence_sets):
+    def propagate_evidence_sets(self, xs, evidence_sets, normalize=False):
         """`propagate` for several hard-evidence sets over the same factor values (no counterpart in the
         reference, whose users loop over `propagate` after slicing the factors, `README.md:155-165`):
         `evidence_sets` is a list of {variable: observed state}; returns one list of factor marginals
         per set, each factor with its full shape (entries contradicting the evidence are zero) and
         every table of set e summing to P(evidence e) * Z.  The clique tables are formed once and
-        shared by all sets; a pass over a table serves eight sets at a time (JTP_MULTISET)."""
+        shared by all sets; a pass over a table serves eight sets at a time (JTP_MULTISET).
+
+        `normalize`: the sets run on an overflow-safe plan (`engine.Plan(scaled=True, share_potentials=True)`: one pass per set
+        over the shared tables - scaled multi-set plans are not built), every marginal is divided by its own sum, and
+        `tree.log_z_sets[e]` is log|Z_e|: log P(evidence e) = log_z_sets[e] - that of a set observing nothing."""
         from . import engine
 
         ct = self.clique_tree
@@ -257,6 +296,18 @@ class JunctionTree:
         # one copy of the tables; eight evidence sets per pass over a table (JTP_MULTISET), marginals formed
         # on demand from the tables and each set's final messages
         from ._capi import UnsupportedStructure
+        if normalize:
+            plan = engine.plan_for(self.tree, node_vars, ct.factor_graph.sizes, "f32" if all_f32 else "f64",
+                                   n_batch=len(evidence_sets), share_potentials=True, scaled=True, cover=self.cover(), **self._opts)
+            plan.evidence_mode = "one pass per evidence set over shared tables (scaled plan: messages divided by powers of two)"
+            self._memo["evidence_plan"] = plan
+            _stage_changed_cliques(plan, ct, xs)
+            for b, observed in enumerate(evidence_sets):
+                plan.set_evidence(observed, batch=b)
+            plan.propagate(0, len(evidence_sets))
+            out = [_normalised(plan.factor_marginals(ct.factor_graph.factors, ct.factor_to_maxclique, batch=b)) for b in range(len(evidence_sets))]
+            self._memo["log_z_sets"] = np.array([plan.log_z(batch=b)[1] for b in range(len(evidence_sets))])
+            return out
         try:
             plan = engine.plan_for(self.tree, node_vars, ct.factor_graph.sizes, "f32" if all_f32 else "f64",
                                    n_batch=len(evidence_sets), multiset=True, **self._opts)
