@@ -277,6 +277,21 @@ int jtp_get_log2_scale(jtp_plan *plan, int32_t batch, int32_t node, int64_t *e);
  * sign 0: *log_abs_z = -inf).  Works on every plan (E = 0 without JTP_SCALED). */
 int jtp_get_log_z(jtp_plan *plan, int32_t batch, double *log_abs_z, int32_t *sign);
 
+/* n_samples joint draws from the beliefs of the last propagate of evidence set `batch`:
+ * states[i * n_vars + v] = state of variable v in sample i (-1: the sample met a slice without mass).
+ * One root-to-leaves sweep over the tree as the description gave it (parent_clique; the root is the clique whose parent is -1):
+ * clique c conditions on the variables it shares with its parent clique - already drawn - and draws its other variables jointly,
+ * as the inverse CDF of that slice of its belief (entries in C order over the drawn variables in the clique's host axis order,
+ * summed in float64) at u = ((splitmix64(key(seed, c) + i)) >> 11) * 2^-53, key as junctiontree_amd/synthetic.py sample_uniform
+ * has it.  Sample i depends on (seed, i) and the beliefs only - not on n_samples, nor on the plan's layout or launch flags - and an
+ * entry that is drawn is never zero.  Observed variables (jtp_set_evidence) come out in their observed state.  Works on JTP_SCALED
+ * plans as it stands (a power of two per clique cancels).
+ * JTP_EUNSUPPORTED: JTP_MULTISET plans, n_ranks > 1, plans in which a clique keeps no table (cover_*).  Where a slice has a zero
+ * or non-finite total, or a negative or NaN entry (evidence of probability zero, overflow), the variables that sample would have
+ * drawn there, and below, are -1; the states are still copied out, the call returns JTP_EINVAL and the message names the number
+ * of such (clique, sample) pairs and the first clique. */
+int jtp_sample(jtp_plan *plan, int32_t batch, int32_t n_samples, uint64_t seed, int32_t *states);
+
 /* ---- instrumentation ------------------------------------------------------------------ */
 
 /* Device timing of the next `keep` propagates with hipEvents on the plan's stream (ring; 0

@@ -797,11 +797,12 @@ struct PlanBuilder {
     int messages();              // message arena, reduce tasks, message offsets of every task
     int schedule();              // launches, workgroup records, exchange schedule
     int finish();                // dataflow segments, sync words, time-stamp region
+    int sampling();              // sampling schedule over the caller's tree (jtp_sample)
     int run() {
         int (PlanBuilder::*stages[])() = {&PlanBuilder::read_description, &PlanBuilder::link_nodes, &PlanBuilder::reroot,
                                           &PlanBuilder::decide_units, &PlanBuilder::binarise, &PlanBuilder::depths, &PlanBuilder::layouts,
                                           &PlanBuilder::arenas, &PlanBuilder::level_work, &PlanBuilder::make_tasks,
-                                          &PlanBuilder::messages, &PlanBuilder::schedule, &PlanBuilder::finish};
+                                          &PlanBuilder::messages, &PlanBuilder::schedule, &PlanBuilder::finish, &PlanBuilder::sampling};
         for (auto stage : stages) {
             const int rc = (this->*stage)();
             if (rc != JTP_OK) return rc;
@@ -2592,6 +2593,49 @@ int PlanBuilder::finish() {
     return JTP_OK;
 }
 
+int PlanBuilder::sampling() {
+    // ---- sampling schedule (jtp_sample): a root-to-leaves sweep over the tree AS THE CALLER DESCRIBED IT.  A clique conditions on the
+    //      variables it shares with its parent clique (K; by the running-intersection property exactly those of its variables some
+    //      clique nearer the root has drawn) and draws the others (F).  Host only: nothing here depends on layouts, so the schedule -
+    //      and with it the order every slice is summed in - is the same whatever the plan's flags.
+    std::vector<int> depth(N, 0), order;
+    std::vector<std::vector<int>> kids(N);
+    int croot = -1;
+    for (int c = 0; c < N; ++c) {
+        if (hp.parent_clique[c] < 0) croot = c;
+        else kids[hp.parent_clique[c]].push_back(c);
+    }
+    order.push_back(croot);
+    for (size_t i = 0; i < order.size(); ++i)
+        for (int k : kids[order[i]]) depth[k] = depth[order[i]] + 1, order.push_back(k);
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return depth[a] != depth[b] ? depth[a] < depth[b] : a < b; });
+    hp.sample.clear();
+    hp.sample_depths.clear();
+    for (int c : order) {
+        SampleClique sc;
+        sc.clique = c;
+        sc.depth = depth[c];
+        const int par = hp.parent_clique[c];
+        for (int v : hp.node_vars[c]) {
+            if (par >= 0 && find_var(hp.node_vars[par], v) >= 0) sc.K.push_back(v);
+            else sc.F.push_back(v), sc.R *= hp.card[v];
+        }
+        if ((int)hp.sample_depths.size() <= sc.depth) hp.sample_depths.resize(sc.depth + 1);
+        hp.sample_depths[sc.depth].push_back((int)hp.sample.size());
+        hp.sample.push_back(sc);
+    }
+    hp.sample_refused.clear();
+    if (hp.multiset) hp.sample_refused = "a multi-set plan keeps no belief tables: sample from a plan made without JTP_MULTISET (one evidence set per pass)";
+    else if (hp.n_ranks > 1) hp.sample_refused = "sampling from a plan shared by several ranks is not built: make the plan with n_ranks = 1";
+    else
+        for (int c = 0; c < N; ++c)
+            if (hp.pn[c].unit) {
+                hp.sample_refused = "clique " + std::to_string(c) + " keeps no table on the device: make the plan without `cover`";
+                break;
+            }
+    return JTP_OK;
+}
+
 int jtp_build_plan(const jtp_tree_desc *d, HostPlan &hp, std::string &err) {
     return PlanBuilder(d, hp, err).run();
 }
@@ -2898,6 +2942,24 @@ void jtp_plan_to_json(HostPlan &hp, bool with_tasks) {
           << ",\"off\":" << c.off << ",\"count\":" << c.count << "}";
     }
     o << "]";
+    o << ",\"sample\":{\"refused\":\"" << json_escape(hp.sample_refused) << "\",\"depths\":[";
+    for (size_t i = 0; i < hp.sample_depths.size(); ++i) {
+        if (i) o << ",";
+        std::vector<int> cl;
+        for (int k : hp.sample_depths[i]) cl.push_back(hp.sample[k].clique);
+        json_vec(o, cl);
+    }
+    o << "],\"cliques\":[";
+    for (size_t i = 0; i < hp.sample.size(); ++i) {
+        const SampleClique &sc = hp.sample[i];
+        if (i) o << ",";
+        o << "{\"clique\":" << sc.clique << ",\"depth\":" << sc.depth << ",\"parent\":" << hp.parent_clique[sc.clique] << ",\"R\":" << sc.R << ",\"K\":";
+        json_vec(o, sc.K);
+        o << ",\"F\":";
+        json_vec(o, sc.F);
+        o << "}";
+    }
+    o << "]}";
     if (hp.scaled) {                  // (plans without JTP_SCALED describe as they always did)
         o << ",\"scaled\":1,\"rescale\":[";
         for (size_t i = 0; i < hp.rescale.size(); ++i) {

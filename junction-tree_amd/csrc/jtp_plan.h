@@ -105,6 +105,27 @@ struct JtRescale {
     int32_t pad;
 };
 
+// jtp_sample: one record per clique of the sampling schedule (SampleClique), read by the kernel jt_sample_level as it stands.  The
+// conditioning variables come first, then the drawn ones, both in host axis order.  A digit's place in the belief table is linear
+// in the digit - the `back` sum of jt_dev_to_host - in two parts for the variable across the thread part's top bit of a compact
+// row (JtPackDesc::split_var): (digit mod 2^lb) * stride + (digit >> lb) * stride2; every other variable has lb = 31, stride2 = 0.
+struct JtSampleVar {                 // 24 bytes
+    int32_t col;                     // column of the state row (variable id)
+    int32_t card;
+    uint32_t stride, stride2;        // device element strides
+    int32_t lb;
+    uint32_t radix;                  // drawn variables: product of the cardinalities of the drawn variables behind this one (C order)
+};
+struct JtSample {
+    int64_t bel_off;                 // element offset of the clique's table in the belief arena
+    int32_t nK, nF;
+    uint32_t R;                      // entries of one slice: product of the cardinalities of the drawn variables
+    int32_t clique;                  // C-ABI clique number: the random stream's key
+    int32_t ord;                     // place in the visit order (the failure report keeps the smallest)
+    int32_t pad;
+    JtSampleVar v[JT_MAX_VARS];      // [0, nK): conditioning; [nK, nK + nF): drawn
+};
+
 // Dataflow schedule: consecutive launches of one phase run as ONE launch whose workgroups take
 // their place in the block list from a ticket counter and wait on message completion counters.
 struct Segment {
@@ -125,7 +146,16 @@ struct PStatic {
     int64_t off = -1;                // doubles, in the fixed arena; -1: the clique is another rank's
 };
 
-struct VirtualFill { JtPackDesc d; };   // all-ones table of a virtual clique (1 where the index names an entry, else 0)
+struct VirtualFill { JtPackDesc d; };
+
+// Sampling schedule (jtp_sample): one entry per clique of the CALLER's tree (parent_clique as given - not the re-rooted, binarised
+// tree of the propagate; beliefs do not depend on the root), in visit order: by depth, then by clique number.
+struct SampleClique {
+    int clique = 0, depth = 0;
+    std::vector<int> K;              // variables shared with the parent clique (drawn before this clique is visited), host axis order
+    std::vector<int> F;              // the others: drawn here, host axis order
+    int64_t R = 1;                   // product of the cardinalities of F: entries of one conditional slice
+};   // all-ones table of a virtual clique (1 where the index names an entry, else 0)
 
 struct HostPlan;
 // decode chunk number -> workgroup record (element base, message bases, partial numbers)
@@ -253,6 +283,9 @@ struct HostPlan {
     double staging_bytes = 0;        // message bytes all workgroups load while staging (partial copies included)
     double table_bytes = 0;          // clique-table bytes all workgroups stream (reads + belief writes)
     int n_messages = 0;
+    std::vector<SampleClique> sample;            // sampling schedule, visit order
+    std::vector<std::vector<int>> sample_depths; // per depth of the caller's tree: indices into `sample`
+    std::string sample_refused;                  // why jtp_sample refuses this plan (JTP_EUNSUPPORTED), or empty
     std::string json;
 };
 

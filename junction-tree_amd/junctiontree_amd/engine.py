@@ -416,6 +416,26 @@ class Plan:
         _capi.check(self._lib.jtp_get_log2_scale(self._handle, batch, self.abi_of[node], C.byref(e)))
         return int(e.value)
 
+    def sample(self, n, seed=0, batch=0):
+        """`n` joint draws from the beliefs of the last propagate of evidence set `batch` (`jtp_sample`): an int32 array
+        (n, len(self.var_labels)), column j the state of variable `self.var_labels[j]`.  One root-to-leaves sweep on the device over
+        the tree as it was given; sample i depends on (seed, i) and the beliefs only (`synthetic.sample_uniform`), so the first rows
+        of a longer call are the rows of a shorter one.  Observed variables come out in their observed state.
+
+        Where samples meet a slice without mass (evidence of probability zero, tables that overflowed) `_capi.JtpError` is raised;
+        its `states` attribute holds the array, with -1 for the variables those samples could not draw."""
+        n = int(n)
+        if n < 1:
+            raise ValueError("n = %d: at least one sample" % n)
+        out = np.zeros((n, len(self.var_labels)), dtype=np.int32)
+        rc = self._lib.jtp_sample(self._handle, int(batch), n, C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), out.ctypes.data_as(C.c_void_p))
+        if rc == _capi.JTP_EINVAL and bool((out < 0).any()):
+            err = _capi.JtpError(self._lib.jtp_last_error().decode("utf-8", "replace"))
+            err.states = out
+            raise err
+        _capi.check(rc)
+        return out
+
     # ------------------------------------------------------------------ instrumentation
     def set_profiling(self, keep=1, per_launch=False, stride=1):
         """Time the next `keep` propagates with hipEvents on the plan's stream: three events per

@@ -49,6 +49,23 @@ def synth_values(seed, node, shape, scale=1.0, dtype=np.float64):
     return ((0.5 + u) * float(scale)).astype(dtype).reshape(shape)
 
 
+_SAMPLE_SALT = np.uint64(0x53414D504C45)
+
+
+def sample_key(seed, clique):
+    """Key of the uniform stream `jtp_sample` draws clique `clique` (C-ABI number) with: the node key, salted so that the stream
+    stays apart from `synth_values` / `jtp_fill_synthetic` called with the same seed."""
+    return splitmix64(np.array([node_key(seed, clique) ^ _SAMPLE_SALT], dtype=np.uint64))[0]
+
+
+def sample_uniform(seed, clique, n):
+    """u(seed, clique, i) in [0, 1) for samples i = 0..n-1, as `jtp_sample` (`engine.Plan.sample`) uses them: counter based, so
+    sample i does not depend on how many samples are drawn."""
+    with np.errstate(over="ignore"):
+        bits = splitmix64(sample_key(seed, clique) + np.arange(int(n), dtype=np.uint64))
+    return (bits >> np.uint64(11)).astype(np.float64) * (1.0 / 9007199254740992.0)
+
+
 # --------------------------------------------------------------------------- tree shapes
 
 def _nest(parent, child_lists, sep_of):
