@@ -139,7 +139,7 @@ typedef struct jtp_stats {
                                        blockIdx order (the default), 2 = dataflow launches in ticket order            */
     int32_t tickets_used;           /* propagates (counted per evidence set) since plan creation that ran in ticket order */
     int32_t flow_propagates;        /* propagates (per evidence set) since plan creation that ran as dataflow launches  */
-    double  device_bytes;           /* device memory the plan allocated at creation (arenas, messages, task tables)     */
+    double  device_bytes;           /* bytes the plan held when jtp_plan_create returned: every buffer, counted as allocated */
     int32_t storage_dtype;          /* JTP_F32 / JTP_F64 the clique tables are stored as: a float32 request is made with float64
                                        tables where the float32 layout cannot be planned (sub-boxes beyond the LDS of a CU) */
     int32_t foreign_seen;           /* propagates since plan creation that found ANOTHER PROCESS with a dataflow propagate in flight
@@ -316,8 +316,14 @@ int jtp_get_launch_ms(jtp_plan *plan, double *ms, int32_t n);
 /* Diagnostic: copy `n` doubles at offset `off` of evidence set `batch`'s message arena to the host. */
 int jtp_debug_read_msg(jtp_plan *plan, int32_t batch, int64_t off, int64_t n, double *host);
 /* Test hooks.  knob "flow_debug": JtFlow::dbg of the following propagates (8 = every dataflow wait times
- * out after 20 ms: exercises the fall-back to one launch per level); "flow": 0 = launch per level from now on. */
+ * out after 20 ms: exercises the fall-back to one launch per level); "flow": 0 = launch per level from now on;
+ * "fail_alloc": see jtp_debug_live_bytes. */
 int jtp_debug_set(jtp_plan *plan, const char *knob, int64_t value);
+/* Test hook: bytes of device memory and of pinned host memory the library holds right now, process-wide (every plan's buffers;
+ * either pointer may be NULL).  With knob "fail_alloc" of jtp_debug_set (the N-th allocation of the plan from now on reports
+ * out of memory on the host; 0 = off) and JTP_FAIL_ALLOC=N in the environment (the same for the allocations of
+ * jtp_plan_create) it lets a test walk every allocation-failure path and see that nothing is left behind. */
+int jtp_debug_live_bytes(int64_t *device_bytes, int64_t *pinned_bytes);
 /* Name of kernel variant i as it appears in rocprofv3 traces, or NULL past the last one. */
 const char *jtp_kernel_name(int32_t variant);
 

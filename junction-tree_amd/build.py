@@ -16,7 +16,7 @@ LIB = os.path.join(LIBDIR, "libjtprop.so")
 # (longest compile first: a worker that frees up takes the next unit in this order, so the short ones fill in at the end)
 INST = ["jtp_inst_%s_%s.hip" % (fam, t) for fam in ("both", "bothm", "level", "mixc", "mix", "flow", "multi", "shape") for t in ("f32", "f64")]
 SOURCES = ["jtp_plan.cpp", "jtp_engine.hip"] + INST       # (compiled in parallel, one object each, then linked)
-DEPS = SOURCES + ["jtp_internal.h", "jtp_plan.h", "jtp_kernels.hip.h", os.path.join("..", "..", "include", "jtprop.h")]
+DEPS = SOURCES + ["jtp_internal.h", "jtp_plan.h", "jtp_kernels.hip.h", "jtp_device.h", os.path.join("..", "..", "include", "jtprop.h")]
 
 
 ID_FILE = os.path.join(LIBDIR, "BUILD_ID")
@@ -72,7 +72,7 @@ def build(force=False, verbose=True, extra=(), out=None, jobs=None):
     os.makedirs(cache, exist_ok=True)
     import hashlib
     headers = {"jtp_plan.cpp": ["jtp_plan.h", "jtp_internal.h", os.path.join("..", "..", "include", "jtprop.h")],
-               "jtp_engine.hip": ["jtp_plan.h", "jtp_internal.h", "jtp_kernels.hip.h", os.path.join("..", "..", "include", "jtprop.h")]}
+               "jtp_engine.hip": ["jtp_plan.h", "jtp_internal.h", "jtp_kernels.hip.h", "jtp_device.h", os.path.join("..", "..", "include", "jtprop.h")]}
     try:                       # (the compiler is part of what an object is made of: a toolchain upgrade must not link old objects)
         toolchain = subprocess.check_output([hipcc, "--version"], stderr=subprocess.STDOUT)
     except (OSError, subprocess.CalledProcessError):

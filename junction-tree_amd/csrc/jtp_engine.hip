@@ -18,10 +18,12 @@
 #include <cstdio>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <vector>
 
+#include "jtp_device.h"
 #include "jtp_kernels.hip.h"
 #include "jtp_plan.h"
 
@@ -39,11 +41,13 @@ static int set_err(int code, const char *fmt, ...) {
     return code;
 }
 
+// the one failure path of HIP calls and of the buffers of jtp_device.h: out of memory is JTP_ENOMEM (the Python layer evicts
+// cached plans and tries again on that), everything else JTP_EHIP
 #define HIP_TRY(expr)                                                                              \
     do {                                                                                           \
         hipError_t _e = (expr);                                                                    \
         if (_e != hipSuccess)                                                                      \
-            return set_err(JTP_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
+            return set_err(_e == hipErrorOutOfMemory ? JTP_ENOMEM : JTP_EHIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
     } while (0)
 
 // ------------------------------------------------------------------------------------------ RCCL (lazy)
@@ -215,6 +219,9 @@ static const char *k_names[JT_K_COUNT] = {
     "jt_multi_flow<T>", "jt_multi_flow<T>", "jt_single<T>", "jt_propagate_flow<T>", "jt_marginals<T>", "jt_lean_single<T>",
 };
 
+// Memory ownership: the plan owns every allocation (jtp_plan: SetMem per evidence set, the *_all arenas of multi-set plans, the
+// tables); BatchBuffers holds plain views of them, set ONCE in jtp_plan_create - where the aliasing is decided (shared psi / fix
+// under JTP_SHARE_POTENTIALS, slices of msg_all / ev_all / sync_all in multi-set plans) - and read by the launch code.
 struct BatchBuffers {
     void *psi = nullptr;
     void *bel = nullptr;
@@ -247,29 +254,21 @@ struct MargBatch {
     // the list is the one the plan was made with (jtp_tree_desc.fold_*) and every request on a clique without a table was folded into
     // the propagate: `d_descs_fold` says where the propagate left them; the unit launches are then skipped (jtp_get_marginals)
     bool folded = false;
-    JtMargDesc *d_descs_fold = nullptr;
+    DeviceBuf<JtMargDesc> d_descs_fold;
     std::vector<JtTask> h_tasks;         // multi-set plans with active lists: the records as planned (readout_redirect patches copies of them)
     std::vector<int32_t> key;            // n, cliques, var_off, var_ids
-    JtTask *d_tasks = nullptr;
-    JtBlock *d_blocks = nullptr;
-    int *d_itab = nullptr;
-    JtMargDesc *d_descs = nullptr;
-    double *scratch = nullptr, *stage = nullptr;
+    DeviceBuf<JtTask> d_tasks;
+    DeviceBuf<JtBlock> d_blocks;
+    DeviceBuf<int> d_itab;
+    DeviceBuf<JtMargDesc> d_descs;
+    DeviceBuf<double> scratch, stage;
     int n = 0, nblocks = 0, lds = 0, max_grid_x = 1;
     // requests on UNIT cliques (no belief table): psi x every incoming table marginalised directly (kernel jt_single); their
     // workgroup records follow the others' in d_blocks
     int unit_nblocks = 0, unit_lds = 0;
     int64_t total_out = 0;
     std::vector<int64_t> elems;          // host entries of each request
-    void release() {
-        if (d_tasks) (void)hipFree(d_tasks);
-        if (d_blocks) (void)hipFree(d_blocks);
-        if (d_itab) (void)hipFree(d_itab);
-        if (d_descs) (void)hipFree(d_descs);
-        if (d_descs_fold) (void)hipFree(d_descs_fold);
-        if (scratch) (void)hipFree(scratch);
-        if (stage) (void)hipFree(stage);
-    }
+    explicit MargBatch(MemLedger *m) : d_descs_fold(m), d_tasks(m), d_blocks(m), d_itab(m), d_descs(m), scratch(m), stage(m) {}
 };
 
 // Plans with a dataflow propagate enqueued and not yet synchronised, per device: dataflow kernels of two plans running
@@ -295,7 +294,17 @@ static hipError_t raise_lds(const void *func, int bytes) {
     return e;
 }
 
+// what one evidence set of a single-set plan owns (multi-set plans: entry 0 holds the shared psi and the belief scratch)
+struct SetMem {
+    DeviceBuf<char> psi, bel;
+    DeviceBuf<double> msg, fix;
+    DeviceBuf<uint32_t> ev, sync;
+    DeviceBuf<int32_t> exps;
+    explicit SetMem(MemLedger *m) : psi(m), bel(m), msg(m), fix(m), ev(m), sync(m), exps(m) {}
+};
+
 struct jtp_plan {
+    MemLedger mem;                  // (first: every buffer below books with it, and is destroyed before it)
     HostPlan hp;
     bool device = false;
     bool widened = false;           // asked for float32 tables, made with float64 ones (jtp_plan_create)
@@ -303,7 +312,8 @@ struct jtp_plan {
     int launch_mode = 0;            // of the last propagate: 0 one launch per level, 1 dataflow in blockIdx order, 2 dataflow, ticket order
     int tickets_used = 0;           // propagates (per evidence set) that ran in ticket order
     int foreign_seen = 0;           // propagates that found ANOTHER PROCESS with a dataflow propagate in flight on the device
-    double device_bytes = 0;        // device memory allocated at plan creation (arenas, message arenas, tables)
+    double device_bytes = 0;        // mem.bytes at the end of jtp_plan_create: everything the plan holds from then on
+    int64_t half = 2;               // doubles per half of a message arena (cur_half)
     int flow_propagates = 0;        // propagates (per evidence set) that ran as dataflow launches
     uint32_t flow_debug = 0;        // JTP_FLOW_DEBUG at plan creation, or jtp_debug_set(plan, "flow_debug", v)
     bool env_tickets = false;       // JTP_FLOW_TICKETS at plan creation
@@ -312,8 +322,8 @@ struct jtp_plan {
     // message arenas, evidence tables and sync areas (bufs[b] point into them; bufs[b].psi/.bel are shared)
     bool multiset = false;
     int n_groups = 0;
-    double *msg_all = nullptr;
-    uint32_t *ev_all = nullptr, *sync_all = nullptr;
+    DeviceBuf<double> msg_all{&mem};
+    DeviceBuf<uint32_t> ev_all{&mem}, sync_all{&mem};
     int64_t set_stride = 0;         // doubles between consecutive sets' arenas (both halves)
     uint32_t ev_stride = 0;         // uint32 per set's evidence table
     // read-out of multi-set plans: belief task of each clique, built on first use
@@ -327,27 +337,33 @@ struct jtp_plan {
     std::vector<uint16_t> act_ids_host;   // [task * cap + j]
     std::vector<int32_t> act_n_host;      // [task]
     std::vector<uint8_t> esum_oct_host;   // [task * n_groups + g]: entries 8 g .. 8 g + 7 of the list observe nothing on the clique's element bits
-    uint8_t *d_member = nullptr, *d_esum_oct = nullptr;
-    uint16_t *d_act_ids = nullptr;
-    int32_t *d_act_n = nullptr;
+    DeviceBuf<uint8_t> d_member{&mem}, d_esum_oct{&mem};
+    DeviceBuf<uint16_t> d_act_ids{&mem};
+    DeviceBuf<int32_t> d_act_n{&mem};
     bool act_dirty = false;
-    JtFanout *d_fanout = nullptr;
-    int n_fanout = 0, cap_fanout = 0;
-    struct BeliefTask { JtTask *d_task = nullptr; JtBlock *d_blk = nullptr; int *d_tab = nullptr; int nblocks = 0, lds = 0; JtTask h_task; };
+    DeviceBuf<JtFanout> d_fanout{&mem};       // (grow-only)
+    int n_fanout = 0;
+    struct BeliefTask {
+        DeviceBuf<JtTask> d_task;
+        DeviceBuf<JtBlock> d_blk;
+        DeviceBuf<int> d_tab;
+        int nblocks = 0, lds = 0;
+        JtTask h_task;
+        explicit BeliefTask(MemLedger *m = nullptr) : d_task(m), d_blk(m), d_tab(m) {}
+    };
     std::vector<BeliefTask> belief_tasks;
     std::vector<hipStream_t> streams;
+    std::vector<SetMem> set_mem;
     std::vector<BatchBuffers> bufs;
-    JtTask *d_tasks = nullptr;
-    JtBlock *d_blocks = nullptr;
-    JtBlock *d_init[2] = {nullptr, nullptr};      // HostPlan::init_blocks on the device (mixed-radix plans)
-    JtRescale *d_rescale = nullptr;               // HostPlan::rescale on the device (JTP_SCALED plans)
-    int *d_itab = nullptr;
-    void *stage = nullptr;          // device staging buffer for host<->device conversion
-    size_t stage_bytes = 0;
+    DeviceBuf<JtTask> d_tasks{&mem};
+    DeviceBuf<JtBlock> d_blocks{&mem};
+    DeviceBuf<JtBlock> d_init[2] = {DeviceBuf<JtBlock>(&mem), DeviceBuf<JtBlock>(&mem)};      // HostPlan::init_blocks on the device (mixed-radix plans)
+    DeviceBuf<JtRescale> d_rescale{&mem};         // HostPlan::rescale on the device (JTP_SCALED plans)
+    DeviceBuf<int> d_itab{&mem};
+    DeviceBuf<char> stage{&mem};    // device staging buffer for host<->device conversion (grow-only)
     // uploads (jtp_set_potential): two device staging buffers used in turn, an event each - a call waits only for
     // the pack kernel that last read ITS buffer (two calls back), not for the stream
-    void *up_stage[2] = {nullptr, nullptr};
-    size_t up_bytes[2] = {0, 0};
+    DeviceBuf<char> up_stage[2] = {DeviceBuf<char>(&mem), DeviceBuf<char>(&mem)};
     hipEvent_t up_ev[2] = {nullptr, nullptr};
     bool up_busy[2] = {false, false};
     unsigned up_cursor = 0;
@@ -362,30 +378,41 @@ struct jtp_plan {
     bool flow = true;               // dataflow launches (one per phase) instead of one per level
     bool chain = false;             // the plan is made of latency-bound levels (JtTask::settle): distribute runs the build without spills
     bool marg_tasks = false;        // some marginal request was folded into the propagate (HostPlan::folded): jt_propagate_flow_marg
-    uint32_t *host_abort = nullptr; // pinned: set by a workgroup that gave up waiting
+    PinnedBuf<uint32_t> host_abort{&mem};     // set by a workgroup that gave up waiting
     int flow_fallbacks = 0;         // times that happened (then: one launch per level from there on)
     int fake_comm = 0;              // JTP_FAKE_COMM: 1 = what a rank would receive is filled with ones, what it would send goes nowhere;
                                     // 2 = the exchange steps run as REAL RCCL groups in loop-back (every ncclSend / ncclRecv of the step
                                     // addressed to this rank itself, on the plan's stream, between the launches as in a sharded run)
     bool esum_dirty = false;        // multi-set plans: JtTask::esum_groups changed on the host since the last upload
     bool psi_dirty = false;         // shared potentials were written (on stream 0) since the last propagate
-    std::vector<MargBatch *> marg_cache;
+    std::vector<std::unique_ptr<MargBatch>> marg_cache;
     // factor tables and records on their way to jt_eval_batch: slices of one buffer handed out in turn, so that
     // evaluate calls following each other need no synchronisation until the buffer wraps
-    char *eval_stage = nullptr;          // device
-    char *eval_host = nullptr;           // pinned mirror: the caller's tables are copied here before the call returns
-    size_t eval_bytes = 0, eval_cursor = 0;
-    void *unit_scratch = nullptr;        // scratch arena in which the belief of a unit clique is formed on demand (jtp_get_belief)
+    DeviceBuf<char> eval_stage{&mem};    // device
+    PinnedBuf<char> eval_host{&mem};     // pinned mirror of the same size: the caller's tables are copied here before the call returns
+    size_t eval_cursor = 0;
+    DeviceBuf<char> unit_scratch{&mem};  // scratch arena in which the belief of a unit clique is formed on demand (jtp_get_belief)
     // jtp_sample: the records of the sampling schedule (HostPlan::sample, visit order), the state rows of one chunk of samples
-    // (int32[sample_cap][n_vars], reused chunk after chunk) and the failure report (count, smallest visit-order place)
-    JtSample *d_sample = nullptr;
-    int32_t *sample_states = nullptr;
-    size_t sample_cap = 0;
-    unsigned long long *d_sample_fail = nullptr;
+    // (int32[rows][n_vars], grow-only, reused chunk after chunk) and the failure report (count, smallest visit-order place)
+    DeviceBuf<JtSample> d_sample{&mem};
+    DeviceBuf<int32_t> sample_states{&mem};
+    DeviceBuf<unsigned long long> d_sample_fail{&mem};
     hipStream_t eval_stream = nullptr;   // stream whose kernels may still read the buffer
     bool eval_pending = false;
     int esize = 4;
 };
+
+// the kernel function of a launch variant / of a dataflow phase in the plan's storage type (raise_lds wants it untyped)
+static const void *kernel_fn(const HostPlan &hp, int variant) {
+    return hp.dtype == JTP_F32 ? (const void *)KernelTable<float>::get(variant, mixk(hp)) : (const void *)KernelTable<double>::get(variant, mixk(hp));
+}
+static const void *flow_fn(const jtp_plan *pl, int phase) {
+    const HostPlan &hp = pl->hp;
+    return hp.dtype == JTP_F32 ? (const void *)KernelTable<float>::get_flow(phase, pl->chain, mixk(hp), pl->marg_tasks)
+                               : (const void *)KernelTable<double>::get_flow(phase, pl->chain, mixk(hp), pl->marg_tasks);
+}
+// offset of the message arena half the last propagate of the evidence set wrote
+static int64_t cur_half(const jtp_plan *pl, const BatchBuffers &b) { return b.cur_off(pl->half); }
 
 // ... and the same across PROCESSES (round 4): every process using this library on a device keeps its count of in-flight
 // dataflow propagates in a slot of a small shared-memory board, /dev/shm/jtprop_flight_<PCI bus id>; a process that finds
@@ -496,32 +523,41 @@ static void leave_flight(jtp_plan *pl) {
 }
 
 static int ensure_stage(jtp_plan *pl, size_t bytes) {
-    if (pl->stage_bytes >= bytes) return JTP_OK;
-    if (pl->stage) HIP_TRY(hipFree(pl->stage));
-    pl->stage = nullptr;
-    pl->stage_bytes = 0;
-    HIP_TRY(hipMalloc(&pl->stage, bytes));
-    pl->stage_bytes = bytes;
+    HIP_TRY(pl->stage.reserve(bytes));
     return JTP_OK;
 }
 
-// messages and marginals are plain bit fields: complete the physical part of their layout record
-static void bitfield_desc(JtPackDesc &d) {
-    for (int i = 0; i < d.nvars; ++i) {
+// messages and marginals are plain bit fields of `nbits` bits: the layout record of one over `vars` (host axis order), variable i
+// at bit pos[i], nb[i] bits wide
+static JtPackDesc bitfield_desc(const HostPlan &hp, const std::vector<int> &vars, const int *pos, const int *nb, int nbits) {
+    JtPackDesc d;
+    memset(&d, 0, sizeof d);
+    d.nvars = (int)vars.size();
+    d.nbits = nbits;
+    int64_t stride = 1;
+    for (int i = d.nvars - 1; i >= 0; --i) {
+        d.pos[i] = (uint8_t)pos[i];
+        d.nb[i] = (uint8_t)nb[i];
+        d.card[i] = hp.card[vars[i]];
+        d.hstride[i] = stride;
+        stride *= hp.card[vars[i]];
         d.dstride[i] = 1u << d.pos[i];
         d.dmod[i] = 1 << d.nb[i];
     }
+    d.host_elems = stride;
     d.phys_elems = (int64_t)1 << d.nbits;
     d.low_bits = d.nbits;
     d.row_elems = 0;
     d.split_var = -1;
+    return d;
 }
+
+// workgroups of 256 threads of a grid-stride kernel over n elements
+static int grid_1d(int64_t n) { return (int)std::min<int64_t>((n + 255) / 256, 4096); }
 
 template <typename T, typename S>
 static void launch_pack(const JtPackDesc &d, const S *stage, T *arena, hipStream_t s) {
-    const int64_t n = d.phys_elems;
-    const int grid = (int)std::min<int64_t>((n + 255) / 256, 4096);
-    hipLaunchKernelGGL((jt_pack<T, S, 0>), dim3(grid), dim3(256), 0, s, d, stage, arena, 0ull, 0.0);
+    hipLaunchKernelGGL((jt_pack<T, S, 0>), dim3(grid_1d(d.phys_elems)), dim3(256), 0, s, d, stage, arena, 0ull, 0.0);
 }
 
 extern "C" {
@@ -532,13 +568,12 @@ const char *jtp_last_error(void) { return g_err.c_str(); }
 #ifndef JTP_SOURCE_ID
 #define JTP_SOURCE_ID "unknown"
 #endif
-const char *jtp_version(void) { return "jtprop 0.8.0 (gfx950, HIP, RCCL p2p) src:" JTP_SOURCE_ID; }
+const char *jtp_version(void) { return "jtprop 0.8.1 (gfx950, HIP, RCCL p2p) src:" JTP_SOURCE_ID; }
 
 int jtp_host_alloc(void **ptr, size_t bytes) {
     if (!ptr) return set_err(JTP_EINVAL, "null argument");
     *ptr = nullptr;
-    hipError_t e = hipHostMalloc(ptr, std::max<size_t>(bytes, 1), hipHostMallocDefault);
-    if (e != hipSuccess) return set_err(e == hipErrorOutOfMemory ? JTP_ENOMEM : JTP_EHIP, "hipHostMalloc(%zu): %s", bytes, hipGetErrorString(e));
+    HIP_TRY(hipHostMalloc(ptr, std::max<size_t>(bytes, 1), hipHostMallocDefault));
     return JTP_OK;
 }
 
@@ -581,6 +616,7 @@ const char *jtp_kernel_name(int32_t variant) {
 
 void jtp_plan_destroy(jtp_plan *pl) {
     if (!pl) return;
+    std::vector<hipStream_t> streams;
     if (pl->device) {
         (void)hipSetDevice(pl->hp.device);
         for (auto s : pl->streams) (void)hipStreamSynchronize(s);
@@ -588,70 +624,27 @@ void jtp_plan_destroy(jtp_plan *pl) {
             pl->inflight = false;
             (void)board::publish(pl->hp.device, --g_inflight[pl->hp.device & 63]);
         }
-        if (pl->multiset) {
-            if (!pl->bufs.empty()) {
-                if (pl->bufs[0].psi) (void)hipFree(pl->bufs[0].psi);
-                if (pl->bufs[0].bel) (void)hipFree(pl->bufs[0].bel);
-            }
-            if (pl->msg_all) (void)hipFree(pl->msg_all);
-            if (pl->d_member) (void)hipFree(pl->d_member);
-            if (pl->d_esum_oct) (void)hipFree(pl->d_esum_oct);
-            if (pl->d_act_ids) (void)hipFree(pl->d_act_ids);
-            if (pl->d_act_n) (void)hipFree(pl->d_act_n);
-            if (pl->d_fanout) (void)hipFree(pl->d_fanout);
-            if (pl->ev_all) (void)hipFree(pl->ev_all);
-            if (pl->sync_all) (void)hipFree(pl->sync_all);
-        } else
-        for (auto &b : pl->bufs) {
-            if (b.psi && (&b == &pl->bufs[0] || b.psi != pl->bufs[0].psi)) (void)hipFree(b.psi);
-            if (b.bel) (void)hipFree(b.bel);
-            if (b.msg) (void)hipFree(b.msg);
-            if (b.fix && (&b == &pl->bufs[0] || b.fix != pl->bufs[0].fix)) (void)hipFree(b.fix);
-            if (b.ev) (void)hipFree(b.ev);
-            if (b.sync) (void)hipFree(b.sync);
-            if (b.exps) (void)hipFree(b.exps);
-        }
-        if (pl->host_abort) (void)hipHostFree(pl->host_abort);
-        for (auto &bt : pl->belief_tasks) {
-            if (bt.d_task) (void)hipFree(bt.d_task);
-            if (bt.d_blk) (void)hipFree(bt.d_blk);
-            if (bt.d_tab) (void)hipFree(bt.d_tab);
-        }
-        for (MargBatch *mb : pl->marg_cache) {
-            mb->release();
-            delete mb;
-        }
-        if (pl->d_tasks) (void)hipFree(pl->d_tasks);
-        if (pl->d_blocks) (void)hipFree(pl->d_blocks);
-        for (int m = 0; m < 2; ++m)
-            if (pl->d_init[m]) (void)hipFree(pl->d_init[m]);
-        if (pl->d_rescale) (void)hipFree(pl->d_rescale);
-        if (pl->d_itab) (void)hipFree(pl->d_itab);
-        if (pl->stage) (void)hipFree(pl->stage);
-        for (int i = 0; i < 2; ++i) {
-            if (pl->up_stage[i]) (void)hipFree(pl->up_stage[i]);
-            if (pl->up_ev[i]) (void)hipEventDestroy(pl->up_ev[i]);
-        }
-        if (pl->eval_stage) (void)hipFree(pl->eval_stage);
-        if (pl->eval_host) (void)hipHostFree(pl->eval_host);
-        if (pl->unit_scratch) (void)hipFree(pl->unit_scratch);
-        if (pl->d_sample) (void)hipFree(pl->d_sample);
-        if (pl->sample_states) (void)hipFree(pl->sample_states);
-        if (pl->d_sample_fail) (void)hipFree(pl->d_sample_fail);
+        for (auto e : pl->up_ev)
+            if (e) (void)hipEventDestroy(e);
         for (auto e : pl->ev) (void)hipEventDestroy(e);
         for (auto e : pl->region_ev)
             if (e) (void)hipEventDestroy(e);
-        for (auto s : pl->streams) (void)hipStreamDestroy(s);
+        streams.swap(pl->streams);
     }
-    delete pl;
+    delete pl;                      // every buffer: after the streams were waited for, before they are destroyed
+    for (auto s : streams) (void)hipStreamDestroy(s);
 }
+struct PlanDestroyer { void operator()(jtp_plan *pl) const { jtp_plan_destroy(pl); } };
 
 static int zero_padding(jtp_plan *pl, double *msg, int nsets, hipStream_t s, int halves = 3);
 
 int jtp_plan_create(const jtp_tree_desc *desc, jtp_plan **out) {
     if (!out) return set_err(JTP_EINVAL, "null output pointer");
     *out = nullptr;
-    jtp_plan *pl = new jtp_plan();
+    // (destroyed on every early return; released into *out at the end)
+    std::unique_ptr<jtp_plan, PlanDestroyer> owner(new jtp_plan());
+    jtp_plan *pl = owner.get();
+    auto start_over = [&]() { owner.reset(new jtp_plan()), pl = owner.get(); };
     std::string err;
     int rc = jtp_build_plan(desc, pl->hp, err);
     // Fall-backs of the planner's defaults, tried in turn while the structure is "unsupported":
@@ -669,8 +662,7 @@ int jtp_plan_create(const jtp_tree_desc *desc, jtp_plan **out) {
         if (relayout) again.layout_policy = 2;
         if (pad) again.flags |= JTP_NO_COMPACT;
         std::string err2;
-        delete pl;
-        pl = new jtp_plan();
+        start_over();
         const int rc2 = jtp_build_plan(&again, pl->hp, err2);
         if (rc2 == JTP_OK) rc = rc2;
         else if (rc2 != JTP_EUNSUPPORTED) rc = rc2, err = err2;
@@ -689,8 +681,7 @@ int jtp_plan_create(const jtp_tree_desc *desc, jtp_plan **out) {
                 again.flags |= JTP_NO_COMPACT;
             }
             std::string err2;
-            delete pl;
-            pl = new jtp_plan();
+            start_over();
             const int rc2 = jtp_build_plan(&again, pl->hp, err2);
             if (rc2 == JTP_OK) rc = rc2, pl->widened = true;
             else if (rc2 != JTP_EUNSUPPORTED) rc = rc2, err = err2;
@@ -703,24 +694,19 @@ int jtp_plan_create(const jtp_tree_desc *desc, jtp_plan **out) {
         again.cover_off = again.cover_ids = nullptr;
         jtp_plan *fresh = nullptr;
         const int rc2 = jtp_plan_create(&again, &fresh);
-        delete pl;
         if (rc2 == JTP_OK) {
             fresh->hp.lean_refused = err.empty() ? std::string("unsupported") : err;      // (jtp_stats.lean_refused, jtp_plan_describe)
             *out = fresh;
         }
         return rc2;
     }
-    if (rc != JTP_OK) {
-        delete pl;
-        return set_err(rc, "%s", err.c_str());
-    }
+    if (rc != JTP_OK) return set_err(rc, "%s", err.c_str());
     HostPlan &hp = pl->hp;
     pl->esize = hp.dtype == JTP_F32 ? 4 : 8;
+    pl->half = std::max<int64_t>(hp.msg_doubles, 2);
     pl->multiset = hp.multiset;
-    if (pl->multiset && !(hp.flags & JTP_SHARE_POTENTIALS)) {
-        delete pl;
+    if (pl->multiset && !(hp.flags & JTP_SHARE_POTENTIALS))
         return set_err(JTP_EINVAL, "JTP_MULTISET needs JTP_SHARE_POTENTIALS (the evidence sets of a group read one table)");
-    }
     // one launch per level when asked for, for per-shape launches and for the JTP_DEBUG experiments
     pl->flow = !(hp.flags & (JTP_LEVEL_LAUNCHES | JTP_SPLIT_VARIANTS)) && !(hp.knobs.debug & 1) && !hp.knobs.force_level_launches;
     // Sub-boxes so large that one or two workgroups fill a CU (config 3: 121 KB): a waiting workgroup
@@ -730,50 +716,43 @@ int jtp_plan_create(const jtp_tree_desc *desc, jtp_plan **out) {
     pl->chain = hp.chain_plan;
     for (const HostPlan::FoldReq &fr : hp.folded) pl->marg_tasks = pl->marg_tasks || fr.task >= 0;
     if (hp.flags & JTP_PLAN_ONLY) {
-        *out = pl;
+        *out = owner.release();
         return JTP_OK;
     }
     // JTP_FAKE_COMM=1 (development aid): run ONE rank's share of a multi-rank plan on its own; what
     // it would receive is filled with ones, what it would send goes nowhere.  Timing only.
     pl->fake_comm = hp.n_ranks > 1 ? hp.knobs.fake_comm : 0;
-    if (pl->fake_comm == 2 && (!rccl::comm || rccl::comm_size != 1)) {
-        delete pl;
+    if (pl->fake_comm == 2 && (!rccl::comm || rccl::comm_size != 1))
         return set_err(JTP_ECOMM, "JTP_FAKE_COMM=2 (exchange steps as RCCL groups in loop-back) needs a communicator of ONE rank: jtp_comm_init(0, 1, ...)");
-    }
-    if (hp.n_ranks > 1 && !pl->fake_comm && (!rccl::comm || rccl::comm_size != hp.n_ranks || rccl::comm_rank != hp.rank)) {
-        delete pl;
+    if (hp.n_ranks > 1 && !pl->fake_comm && (!rccl::comm || rccl::comm_size != hp.n_ranks || rccl::comm_rank != hp.rank))
         return set_err(JTP_ECOMM, "n_ranks=%d but jtp_comm_init was not called with a matching communicator", hp.n_ranks);
-    }
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev <= 0) {
-        delete pl;
+    if (e != hipSuccess || ndev <= 0)
         return set_err(JTP_EHIP, "no HIP device available (%s); libjtprop has no CPU fallback",
                        e != hipSuccess ? hipGetErrorString(e) : "device count is 0");
-    }
-#define CREATE_TRY(expr)                                                                                 \
-    do {                                                                                                 \
-        hipError_t _e = (expr);                                                                          \
-        if (_e != hipSuccess) {                                                                          \
-            set_err(_e == hipErrorOutOfMemory ? JTP_ENOMEM : JTP_EHIP, "%s failed: %s", #expr, hipGetErrorString(_e)); \
-            jtp_plan_destroy(pl);                                                                        \
-            return _e == hipErrorOutOfMemory ? JTP_ENOMEM : JTP_EHIP;                                    \
-        }                                                                                                \
-    } while (0)
     pl->device = true;
+    pl->mem.fail_in = hp.knobs.fail_alloc;          // (test hook: for the allocations of this function only)
     pl->flow_debug = hp.knobs.flow_debug;
     pl->env_tickets = hp.knobs.flow_tickets != 0;
     pl->roctx = hp.knobs.roctx != 0;
     if (pl->roctx) roctx::load();
-    CREATE_TRY(hipSetDevice(hp.device));
+    HIP_TRY(hipSetDevice(hp.device));
     const int nstreams = pl->multiset ? 1 : std::min(hp.n_batch, 16);
     pl->streams.resize(nstreams);
-    for (auto &s : pl->streams) CREATE_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    for (auto &s : pl->streams) HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    hipStream_t s0 = pl->streams[0];
     pl->bufs.resize(hp.n_batch);
     const size_t abytes = (size_t)std::max<int64_t>(hp.arena_elems, 256) * pl->esize;
     // two halves, used by alternate propagates (jtp_internal.h: JT_UNWRITTEN)
-    const size_t mbytes = (size_t)std::max<int64_t>(hp.msg_doubles, 2) * 8 * 2;
+    const size_t mdoubles = (size_t)pl->half * 2, mbytes = mdoubles * 8;
+    const int unwritten = (int)(uint32_t)(JT_UNWRITTEN & 0xffffffffu);
     const bool share_psi = (hp.flags & JTP_SHARE_POTENTIALS) != 0;     // one potential arena for all evidence sets
+    // Which evidence set sees which allocation is decided HERE, once: multi-set plans share psi and one belief scratch (set_mem[0])
+    // and slice the *_all arenas; single-set plans own everything per set, except psi / fix under JTP_SHARE_POTENTIALS (set 0's).
+    const size_t n_own = pl->multiset ? 1 : (size_t)hp.n_batch;
+    pl->set_mem.reserve(n_own);
+    for (size_t i = 0; i < n_own; ++i) pl->set_mem.emplace_back(&pl->mem);
     if (pl->multiset) {
         // (group 0: the evidence-free sets the others take their untouched upward messages from - one more group through the collect
         //  pass, which pays from eight groups on: measured 64 sets 4.97 -> 4.8 ms, 8 sets 0.91 -> 1.3; JTP_EF_SHARE=1 / JTP_NO_EF_SHARE=1 force it)
@@ -781,142 +760,106 @@ int jtp_plan_create(const jtp_tree_desc *desc, jtp_plan **out) {
         pl->set0 = ef ? JT_MSETS : 0;
         pl->n_groups = (hp.n_batch + JT_MSETS - 1) / JT_MSETS + (pl->set0 ? 1 : 0);
         const size_t nsets = (size_t)pl->n_groups * JT_MSETS;          // (the last group is padded with evidence-free sets)
-        pl->set_stride = (int64_t)(mbytes / 8);
+        pl->set_stride = (int64_t)mdoubles;
         pl->ev_stride = (uint32_t)(2 * hp.pn.size());
-        void *psi = nullptr, *bel = nullptr;
-        CREATE_TRY(hipMalloc(&psi, abytes));
-        pl->bufs[0].psi = psi;
-        CREATE_TRY(hipMalloc(&bel, abytes));                           // scratch: one belief table at a time, on demand
-        pl->bufs[0].bel = bel;
-        CREATE_TRY(hipMemsetAsync(psi, 0, abytes, pl->streams[0]));
-        CREATE_TRY(hipMemsetAsync(bel, 0, abytes, pl->streams[0]));
-        CREATE_TRY(hipMalloc((void **)&pl->msg_all, mbytes * nsets));
-        CREATE_TRY(hipMemsetD32Async((hipDeviceptr_t)pl->msg_all, (int)(uint32_t)(JT_UNWRITTEN & 0xffffffffu), mbytes * nsets / 4, pl->streams[0]));
-        CREATE_TRY(hipMalloc((void **)&pl->ev_all, (size_t)pl->ev_stride * 4 * nsets));
-        CREATE_TRY(hipMemsetAsync(pl->ev_all, 0, (size_t)pl->ev_stride * 4 * nsets, pl->streams[0]));
-        CREATE_TRY(hipMalloc((void **)&pl->sync_all, (size_t)hp.sync_words * 4 * pl->n_groups));
-        CREATE_TRY(hipMemsetAsync(pl->sync_all, 0, (size_t)hp.sync_words * 4 * pl->n_groups, pl->streams[0]));
+        SetMem &m = pl->set_mem[0];
+        HIP_TRY(m.psi.alloc(abytes));
+        HIP_TRY(m.bel.alloc(abytes));                                  // scratch: one belief table at a time, on demand
+        HIP_TRY(hipMemsetAsync(m.psi.get(), 0, abytes, s0));
+        HIP_TRY(hipMemsetAsync(m.bel.get(), 0, abytes, s0));
+        HIP_TRY(pl->msg_all.alloc(mdoubles * nsets));
+        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)pl->msg_all.get(), unwritten, mbytes * nsets / 4, s0));
+        HIP_TRY(pl->ev_all.alloc((size_t)pl->ev_stride * nsets));
+        HIP_TRY(hipMemsetAsync(pl->ev_all.get(), 0, pl->ev_all.bytes(), s0));
+        HIP_TRY(pl->sync_all.alloc((size_t)hp.sync_words * pl->n_groups));
+        HIP_TRY(hipMemsetAsync(pl->sync_all.get(), 0, pl->sync_all.bytes(), s0));
         for (int b = 0; b < hp.n_batch; ++b) {
             BatchBuffers &bb = pl->bufs[b];
-            bb.psi = psi;
-            bb.bel = bel;
-            bb.msg = pl->msg_all + (int64_t)(pl->set0 + b) * pl->set_stride;
-            bb.ev = pl->ev_all + (size_t)(pl->set0 + b) * pl->ev_stride;
-            bb.sync = pl->sync_all + (size_t)((pl->set0 + b) / JT_MSETS) * hp.sync_words;
+            bb.psi = m.psi.get();
+            bb.bel = m.bel.get();
+            bb.msg = pl->msg_all.get() + (int64_t)(pl->set0 + b) * pl->set_stride;
+            bb.ev = pl->ev_all.get() + (size_t)(pl->set0 + b) * pl->ev_stride;
+            bb.sync = pl->sync_all.get() + (size_t)((pl->set0 + b) / JT_MSETS) * hp.sync_words;
         }
-        pl->belief_tasks.resize(hp.pn.size());
         if (pl->set0) {
             // (the active lists are made by the first propagate: rebuild_active)
             const size_t cap = (size_t)pl->n_groups * JT_MSETS, nt = hp.tasks.size();
-            CREATE_TRY(hipMalloc((void **)&pl->d_member, nt * cap));
-            CREATE_TRY(hipMalloc((void **)&pl->d_act_ids, nt * cap * sizeof(uint16_t)));
-            CREATE_TRY(hipMalloc((void **)&pl->d_act_n, nt * sizeof(int32_t)));
-            CREATE_TRY(hipMalloc((void **)&pl->d_esum_oct, nt * (size_t)pl->n_groups));
+            HIP_TRY(pl->d_member.alloc(nt * cap));
+            HIP_TRY(pl->d_act_ids.alloc(nt * cap));
+            HIP_TRY(pl->d_act_n.alloc(nt));
+            HIP_TRY(pl->d_esum_oct.alloc(nt * (size_t)pl->n_groups));
             pl->act_dirty = true;
         }
     } else
-    for (auto &b : pl->bufs) {
-        if (share_psi && &b != &pl->bufs[0]) b.psi = pl->bufs[0].psi;
-        else CREATE_TRY(hipMalloc(&b.psi, abytes));
-        CREATE_TRY(hipMalloc(&b.bel, abytes));
-        CREATE_TRY(hipMalloc((void **)&b.msg, mbytes));
-        if (hp.fix_doubles > 0) {
-            if (share_psi && &b != &pl->bufs[0]) b.fix = pl->bufs[0].fix;
-            else {
-                CREATE_TRY(hipMalloc((void **)&b.fix, (size_t)hp.fix_doubles * 8));
-                CREATE_TRY(hipMemsetAsync(b.fix, 0, (size_t)hp.fix_doubles * 8, pl->streams[0]));
-            }
+    for (size_t i = 0; i < n_own; ++i) {
+        SetMem &m = pl->set_mem[i], &first = pl->set_mem[0];
+        BatchBuffers &b = pl->bufs[i];
+        const bool own_psi = !share_psi || i == 0;
+        if (own_psi) HIP_TRY(m.psi.alloc(abytes));
+        HIP_TRY(m.bel.alloc(abytes));
+        HIP_TRY(m.msg.alloc(mdoubles));
+        if (hp.fix_doubles > 0 && own_psi) {
+            HIP_TRY(m.fix.alloc((size_t)hp.fix_doubles));
+            HIP_TRY(hipMemsetAsync(m.fix.get(), 0, m.fix.bytes(), s0));
         }
-        CREATE_TRY(hipMemsetAsync(b.psi, 0, abytes, pl->streams[0]));
-        CREATE_TRY(hipMemsetAsync(b.bel, 0, abytes, pl->streams[0]));
-        CREATE_TRY(hipMemsetD32Async((hipDeviceptr_t)b.msg, (int)(uint32_t)(JT_UNWRITTEN & 0xffffffffu), mbytes / 4, pl->streams[0]));
-        CREATE_TRY(hipMalloc((void **)&b.sync, (size_t)hp.sync_words * 4));
-        CREATE_TRY(hipMemsetAsync(b.sync, 0, (size_t)hp.sync_words * 4, pl->streams[0]));
+        b.psi = (own_psi ? m : first).psi.get();
+        b.fix = (own_psi ? m : first).fix.get();
+        b.bel = m.bel.get();
+        b.msg = m.msg.get();
+        HIP_TRY(hipMemsetAsync(b.psi, 0, abytes, s0));
+        HIP_TRY(hipMemsetAsync(b.bel, 0, abytes, s0));
+        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)b.msg, unwritten, mbytes / 4, s0));
+        HIP_TRY(m.sync.alloc((size_t)hp.sync_words));
+        b.sync = m.sync.get();
+        HIP_TRY(hipMemsetAsync(b.sync, 0, m.sync.bytes(), s0));
         if (hp.scaled) {
-            const size_t ebytes = std::max<size_t>(2 * hp.ps.size(), 1) * sizeof(int32_t);
-            CREATE_TRY(hipMalloc((void **)&b.exps, ebytes));
-            CREATE_TRY(hipMemsetAsync(b.exps, 0, ebytes, pl->streams[0]));
+            HIP_TRY(m.exps.alloc(std::max<size_t>(2 * hp.ps.size(), 1)));
+            b.exps = m.exps.get();
+            HIP_TRY(hipMemsetAsync(b.exps, 0, m.exps.bytes(), s0));
         }
     }
-    CREATE_TRY(hipHostMalloc((void **)&pl->host_abort, 64, hipHostMallocMapped));
-    *pl->host_abort = 0;
+    HIP_TRY(pl->host_abort.alloc(16, hipHostMallocMapped));
+    *pl->host_abort.get() = 0;
 
     for (auto &b : pl->bufs) {
         if (&b != &pl->bufs[0] && b.psi == pl->bufs[0].psi) continue;          // shared tables: filled once
         for (const VirtualFill &vf : hp.virtual_fills) {
-            const int64_t n = vf.d.phys_elems;
-            const int grid = (int)std::min<int64_t>((n + 255) / 256, 4096);
-            if (hp.dtype == JTP_F32) hipLaunchKernelGGL((jt_pack<float, float, 2>), dim3(grid), dim3(256), 0, pl->streams[0], vf.d, (const float *)nullptr, (float *)b.psi, 0ull, 1.0);
-            else hipLaunchKernelGGL((jt_pack<double, double, 2>), dim3(grid), dim3(256), 0, pl->streams[0], vf.d, (const double *)nullptr, (double *)b.psi, 0ull, 1.0);
+            const int grid = grid_1d(vf.d.phys_elems);
+            if (hp.dtype == JTP_F32) hipLaunchKernelGGL((jt_pack<float, float, 2>), dim3(grid), dim3(256), 0, s0, vf.d, (const float *)nullptr, (float *)b.psi, 0ull, 1.0);
+            else hipLaunchKernelGGL((jt_pack<double, double, 2>), dim3(grid), dim3(256), 0, s0, vf.d, (const double *)nullptr, (double *)b.psi, 0ull, 1.0);
         }
-        CREATE_TRY(hipGetLastError());
+        HIP_TRY(hipGetLastError());
     }
     if (pl->multiset) {
         pl->ev_host.assign((size_t)pl->ev_stride * pl->n_groups * JT_MSETS, 0u);
         for (JtTask &tk : hp.tasks)
             if (tk.esum & 1) tk.esum |= 2, tk.esum_groups = ~0ull;      // no evidence yet
     }
-    if (!hp.tasks.empty()) {
-        CREATE_TRY(hipMalloc((void **)&pl->d_tasks, hp.tasks.size() * sizeof(JtTask)));
-        CREATE_TRY(hipMemcpy(pl->d_tasks, hp.tasks.data(), hp.tasks.size() * sizeof(JtTask), hipMemcpyHostToDevice));
-    }
-    if (!hp.blocks.empty()) {
-        CREATE_TRY(hipMalloc((void **)&pl->d_blocks, hp.blocks.size() * sizeof(JtBlock)));
-        CREATE_TRY(hipMemcpy(pl->d_blocks, hp.blocks.data(), hp.blocks.size() * sizeof(JtBlock), hipMemcpyHostToDevice));
-    }
-    if (!hp.itab.empty()) {
-        CREATE_TRY(hipMalloc((void **)&pl->d_itab, hp.itab.size() * sizeof(int32_t)));
-        CREATE_TRY(hipMemcpy(pl->d_itab, hp.itab.data(), hp.itab.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    }
-    if (!hp.rescale.empty()) {
-        CREATE_TRY(hipMalloc((void **)&pl->d_rescale, hp.rescale.size() * sizeof(JtRescale)));
-        CREATE_TRY(hipMemcpy(pl->d_rescale, hp.rescale.data(), hp.rescale.size() * sizeof(JtRescale), hipMemcpyHostToDevice));
-    }
-    for (int m = 0; m < 2; ++m)
-        if (!hp.init_blocks[m].empty()) {
-            CREATE_TRY(hipMalloc((void **)&pl->d_init[m], hp.init_blocks[m].size() * sizeof(JtBlock)));
-            CREATE_TRY(hipMemcpy(pl->d_init[m], hp.init_blocks[m].data(), hp.init_blocks[m].size() * sizeof(JtBlock), hipMemcpyHostToDevice));
-        }
+    HIP_TRY(pl->d_tasks.upload(hp.tasks));
+    HIP_TRY(pl->d_blocks.upload(hp.blocks));
+    HIP_TRY(pl->d_itab.upload(hp.itab));
+    HIP_TRY(pl->d_rescale.upload(hp.rescale));
+    for (int m = 0; m < 2; ++m) HIP_TRY(pl->d_init[m].upload(hp.init_blocks[m]));
     // dynamic LDS beyond 64 KiB has to be allowed per kernel function (raise_lds remembers what each one has)
-    auto kfunc = [&](int v) { return hp.dtype == JTP_F32 ? (const void *)KernelTable<float>::get(v, mixk(hp)) : (const void *)KernelTable<double>::get(v, mixk(hp)); };
     if (pl->multiset) {
-        CREATE_TRY(raise_lds(kfunc(JT_K_MULTI_COLLECT), JT_RING_BYTES + JT_MSETS * (JT_MSETS > 8 ? JT_SETB_SMALL : JT_SETB_LARGE)));
+        HIP_TRY(raise_lds(kernel_fn(hp, JT_K_MULTI_COLLECT), JT_RING_BYTES + JT_MSETS * (JT_MSETS > 8 ? JT_SETB_SMALL : JT_SETB_LARGE)));
     } else if (hp.max_lds > 64 * 1024) {
         for (int v = 0; v < JT_K_COUNT; ++v) {
-            if (kfunc(v) == nullptr) continue;                 // (the dataflow kernels: below)
-            CREATE_TRY(raise_lds(kfunc(v), hp.max_lds));
+            if (kernel_fn(hp, v) == nullptr) continue;             // (the dataflow kernels: below)
+            HIP_TRY(raise_lds(kernel_fn(hp, v), hp.max_lds));
         }
-        for (int ph = 0; ph < 3; ++ph) {
-            const void *f = hp.dtype == JTP_F32 ? (const void *)KernelTable<float>::get_flow(ph, pl->chain, mixk(hp), pl->marg_tasks) : (const void *)KernelTable<double>::get_flow(ph, pl->chain, mixk(hp), pl->marg_tasks);
-            CREATE_TRY(raise_lds(f, hp.max_lds));
-        }
-    }
-    {   // what the plan holds on the device from now on (the plan cache of the Python layer budgets with it)
-        double b = 0;
-        if (pl->multiset) {
-            const size_t nsets = (size_t)pl->n_groups * JT_MSETS;
-            b = 2.0 * abytes + (double)mbytes * nsets + (double)pl->ev_stride * 4 * nsets + (double)hp.sync_words * 4 * pl->n_groups;
-        } else {
-            const size_t npsi = share_psi ? 1 : pl->bufs.size();
-            b = (double)abytes * (npsi + pl->bufs.size()) + ((double)mbytes + (double)hp.sync_words * 4) * pl->bufs.size() + (double)hp.fix_doubles * 8 * npsi;
-        }
-        b += (double)hp.tasks.size() * sizeof(JtTask) + (double)hp.blocks.size() * sizeof(JtBlock) + (double)hp.itab.size() * 4;
-        pl->device_bytes = b;
+        for (int ph = 0; ph < 3; ++ph) HIP_TRY(raise_lds(flow_fn(pl, ph), hp.max_lds));
     }
     if (pl->multiset) {
-        if (int rc = zero_padding(pl, pl->msg_all, pl->n_groups * JT_MSETS, pl->streams[0])) {
-            jtp_plan_destroy(pl);
-            return rc;
-        }
+        if (int rc = zero_padding(pl, pl->msg_all.get(), pl->n_groups * JT_MSETS, s0)) return rc;
     } else
         for (auto &b : pl->bufs)
-            if (int rc = zero_padding(pl, b.msg, 1, pl->streams[0])) {
-                jtp_plan_destroy(pl);
-                return rc;
-            }
-    CREATE_TRY(hipStreamSynchronize(pl->streams[0]));
-#undef CREATE_TRY
-    *out = pl;
+            if (int rc = zero_padding(pl, b.msg, 1, s0)) return rc;
+    HIP_TRY(hipStreamSynchronize(s0));
+    // what the plan holds on the device from now on (the plan cache of the Python layer budgets with it)
+    pl->device_bytes = (double)pl->mem.bytes;
+    pl->mem.fail_in = 0;
+    *out = owner.release();
     return JTP_OK;
 }
 
@@ -985,14 +928,8 @@ int jtp_set_potential(jtp_plan *pl, int32_t batch, int32_t node, const void *hos
         HIP_TRY(hipEventSynchronize(pl->up_ev[ui]));
         pl->up_busy[ui] = false;
     }
-    if (pl->up_bytes[ui] < hbytes) {
-        if (pl->up_stage[ui]) HIP_TRY(hipFree(pl->up_stage[ui]));
-        pl->up_stage[ui] = nullptr;
-        pl->up_bytes[ui] = 0;
-        HIP_TRY(hipMalloc(&pl->up_stage[ui], std::max<size_t>(hbytes, 256)));
-        pl->up_bytes[ui] = std::max<size_t>(hbytes, 256);
-    }
-    void *stage = pl->up_stage[ui];
+    HIP_TRY(pl->up_stage[ui].reserve(std::max<size_t>(hbytes, 256)));
+    void *stage = pl->up_stage[ui].get();
     hipStream_t s = pl->streams[batch % pl->streams.size()];
     // (from pageable memory the copy returns once the runtime has staged the caller's bytes; from page-locked
     //  memory - jtp_host_alloc - it is asynchronous and the caller must keep the array alive until jtp_sync)
@@ -1158,23 +1095,21 @@ int jtp_set_potential_products(jtp_plan *pl, int32_t batch, int32_t n, const int
         pl->eval_pending = false;
         pl->eval_cursor = 0;
     }
-    if (pl->eval_cursor + bytes > pl->eval_bytes) {
+    if (pl->eval_cursor + bytes > pl->eval_stage.size()) {
         if (pl->eval_pending) HIP_TRY(hipStreamSynchronize(pl->eval_stream));
         pl->eval_pending = false;
         pl->eval_cursor = 0;
-        if (bytes > pl->eval_bytes) {
-            if (pl->eval_stage) HIP_TRY(hipFree(pl->eval_stage));
-            if (pl->eval_host) HIP_TRY(hipHostFree(pl->eval_host));
-            pl->eval_stage = pl->eval_host = nullptr;
-            pl->eval_bytes = 0;
+        if (bytes > pl->eval_stage.size()) {               // (the pair is there whole or not at all)
             const size_t want = std::max<size_t>(bytes, (size_t)8 << 20);
-            HIP_TRY(hipMalloc((void **)&pl->eval_stage, want));
-            HIP_TRY(hipHostMalloc((void **)&pl->eval_host, want, hipHostMallocDefault));
-            pl->eval_bytes = want;
+            pl->eval_host.reset();
+            hipError_t e = pl->eval_stage.alloc(want);
+            if (e == hipSuccess) e = pl->eval_host.alloc(want);
+            if (e != hipSuccess) pl->eval_stage.reset();
+            HIP_TRY(e);
         }
     }
-    char *stage = pl->eval_stage + pl->eval_cursor;
-    char *hstage = pl->eval_host + pl->eval_cursor;
+    char *stage = pl->eval_stage.get() + pl->eval_cursor;
+    char *hstage = pl->eval_host.get() + pl->eval_cursor;
     pl->eval_cursor += bytes;
     pl->eval_stream = s;
     pl->eval_pending = true;
@@ -1238,8 +1173,7 @@ int jtp_fill_synthetic(jtp_plan *pl, int32_t batch, uint64_t seed, const double 
         const JtPackDesc &d = hp.pn[c].unit ? hp.stat_pack[c] : hp.pack[c];
         const uint64_t key = host_splitmix64(seed * 0x100000001B3ull + (uint64_t)c);
         const double sc = scale ? scale[c] : 1.0;
-        const int64_t n = d.phys_elems;
-        const int grid = (int)std::min<int64_t>((n + 255) / 256, 4096);
+        const int grid = grid_1d(d.phys_elems);
         if (hp.pn[c].unit)       // (the static table: the same counter-based values over the covered shape)
             hipLaunchKernelGGL((jt_pack<double, double, 1>), dim3(grid), dim3(256), 0, s, d, (const double *)nullptr, b.fix, key, sc);
         else if (hp.dtype == JTP_F32)
@@ -1264,6 +1198,13 @@ static int launch_variant(jtp_plan *pl, int variant, int nblocks, int lds, hipSt
         hipLaunchKernelGGL(f, dim3(nblocks), dim3(JT_THREADS), lds, s, tasks, blocks, itab, (const double *)psi, (double *)bel, msg, fl);
     }
     return JTP_OK;
+}
+
+// read-out launches: their dynamic LDS is only known now, and must be allowed for the kernel first
+static int launch_readout(jtp_plan *pl, int variant, int nblocks, int lds, hipStream_t s, const JtTask *tasks,
+                          const JtBlock *blocks, const int *itab, void *psi, void *bel, double *msg, const JtFlow &fl) {
+    HIP_TRY(raise_lds(kernel_fn(pl->hp, variant), lds));
+    return launch_variant(pl, variant, nblocks, lds, s, tasks, blocks, itab, psi, bel, msg, fl);
 }
 
 // The chunks whose own digits do not exist (a digit beyond a variable's cardinality, a padding bit set) are not in the block
@@ -1457,13 +1398,12 @@ __global__ __launch_bounds__(256) void jt_sample_level(const JtSample *__restric
 // (`msg`, `nsets`: one evidence set's arena, or - multi-set plans - all of them, set_stride doubles apart; `halves`: bit h = arena half h)
 static int zero_padding(jtp_plan *pl, double *msg, int nsets, hipStream_t s, int halves) {
     const HostPlan &hp = pl->hp;
-    const int64_t half = std::max<int64_t>(hp.msg_doubles, 2);
     for (int m = 0; m < 2; ++m) {
         if (hp.init_blocks[m].empty() || !pl->d_init[m]) continue;
         for (int h = 0; h < 2; ++h)
             if ((halves >> h) & 1)
-                hipLaunchKernelGGL(jt_zero_copies, dim3((unsigned)hp.init_blocks[m].size(), (unsigned)nsets), dim3(256), 0, s, pl->d_tasks, pl->d_init[m], msg,
-                                   h ? half : (int64_t)0, pl->set_stride);
+                hipLaunchKernelGGL(jt_zero_copies, dim3((unsigned)hp.init_blocks[m].size(), (unsigned)nsets), dim3(256), 0, s, pl->d_tasks.get(), pl->d_init[m].get(), msg,
+                                   h ? pl->half : (int64_t)0, pl->set_stride);
     }
     HIP_TRY(hipGetLastError());
     return JTP_OK;
@@ -1476,14 +1416,14 @@ static int zero_padding(jtp_plan *pl, double *msg, int nsets, hipStream_t s, int
 // `synced`: the evidence set whose stream the caller has just synchronised (-1: all of them).
 static int check_flow(jtp_plan *pl, int synced = -1) {
     if (!pl->host_abort) return JTP_OK;
-    if (*(volatile uint32_t *)pl->host_abort == 0) {
+    if (*(volatile uint32_t *)pl->host_abort.get() == 0) {
         // only what has actually finished is known to be good (sets sharing the stream finished with it)
         for (size_t i = 0; i < pl->bufs.size(); ++i)
             if (synced < 0 || i % pl->streams.size() == (size_t)synced % pl->streams.size()) pl->bufs[i].unchecked = false;
         leave_flight(pl);
         return JTP_OK;
     }
-    *(volatile uint32_t *)pl->host_abort = 0;
+    *(volatile uint32_t *)pl->host_abort.get() = 0;
     pl->flow = false;
     pl->flow_fallbacks++;
     if (pl->hp.n_ranks > 1) {
@@ -1499,10 +1439,9 @@ static int check_flow(jtp_plan *pl, int synced = -1) {
     // only the sets that are run again lose their messages: a set whose propagate was already checked keeps
     // its arena (its separator beliefs are read from there), and no later launch of this plan waits on markers
     if (pl->multiset) {                                     // (all sets run together, the padding sets of the last group too)
-        const size_t mbytes = (size_t)std::max<int64_t>(pl->hp.msg_doubles, 2) * 16;
         // (on the plan's stream, like the zeros that follow: that stream does not synchronise with the null stream)
-        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)pl->msg_all, (int)(uint32_t)(JT_UNWRITTEN & 0xffffffffu), mbytes * pl->n_groups * JT_MSETS / 4, pl->streams[0]));
-        if (int rc = zero_padding(pl, pl->msg_all, pl->n_groups * JT_MSETS, pl->streams[0])) return rc;
+        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)pl->msg_all.get(), (int)(uint32_t)(JT_UNWRITTEN & 0xffffffffu), pl->msg_all.bytes() / 4, pl->streams[0]));
+        if (int rc = zero_padding(pl, pl->msg_all.get(), pl->n_groups * JT_MSETS, pl->streams[0])) return rc;
         HIP_TRY(hipStreamSynchronize(pl->streams[0]));
         for (auto &b : pl->bufs) b.epoch = 0, b.flow_runs = 0, b.ticket_runs = 0;
     } else
@@ -1510,7 +1449,7 @@ static int check_flow(jtp_plan *pl, int synced = -1) {
         BatchBuffers &b = pl->bufs[i];
         if (!b.unchecked) continue;
         HIP_TRY(hipMemsetAsync(b.sync, 0, (size_t)pl->hp.sync_words * 4, pl->streams[0]));
-        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)b.msg, (int)(uint32_t)(JT_UNWRITTEN & 0xffffffffu), (size_t)std::max<int64_t>(pl->hp.msg_doubles, 2) * 4, pl->streams[0]));
+        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)b.msg, (int)(uint32_t)(JT_UNWRITTEN & 0xffffffffu), (size_t)pl->half * 4, pl->streams[0]));
         if (int rc = zero_padding(pl, b.msg, 1, pl->streams[0])) return rc;
         HIP_TRY(hipStreamSynchronize(pl->streams[0]));
         b.epoch = 0;
@@ -1520,7 +1459,7 @@ static int check_flow(jtp_plan *pl, int synced = -1) {
     if (pl->multiset) {
         bool any = false;
         for (auto &b : pl->bufs) any = any || b.unchecked, b.unchecked = false;
-        HIP_TRY(hipMemset(pl->sync_all, 0, (size_t)pl->hp.sync_words * 4 * pl->n_groups));
+        HIP_TRY(hipMemset(pl->sync_all.get(), 0, pl->sync_all.bytes()));
         if (any) {
             int rc = jtp_propagate(pl, 0, pl->hp.n_batch);
             if (rc) return rc;
@@ -1546,10 +1485,17 @@ static int settle(jtp_plan *pl, int batch) {
     return check_flow(pl, batch);
 }
 
+int jtp_debug_live_bytes(int64_t *device_bytes, int64_t *pinned_bytes) {
+    if (device_bytes) *device_bytes = g_live_bytes[0].load();
+    if (pinned_bytes) *pinned_bytes = g_live_bytes[1].load();
+    return JTP_OK;
+}
+
 int jtp_debug_set(jtp_plan *pl, const char *knob, int64_t value) {
     if (!pl || !knob) return set_err(JTP_EINVAL, "null argument");
     if (!strcmp(knob, "flow_debug")) pl->flow_debug = (uint32_t)value;      // fault injection (tests): see JtFlow::dbg
     else if (!strcmp(knob, "flow")) pl->flow = value != 0 && !pl->hp.segments.empty();
+    else if (!strcmp(knob, "fail_alloc")) pl->mem.fail_in = std::max<int64_t>(value, 0);      // (MemLedger::fail_in)
     else return set_err(JTP_EINVAL, "unknown knob %s", knob);
     return JTP_OK;
 }
@@ -1585,7 +1531,10 @@ int jtp_set_evidence(jtp_plan *pl, int32_t batch, int32_t n, const int32_t *var_
     HIP_TRY(hipSetDevice(hp.device));
     hipStream_t s = pl->streams[batch % pl->streams.size()];
     HIP_TRY(hipStreamSynchronize(s));                      // a propagate in flight may still read the old table
-    if (!b.ev) HIP_TRY(hipMalloc((void **)&b.ev, ev.size() * sizeof(uint32_t)));      // (multi-set plans: a slice of ev_all)
+    if (!b.ev) {                                            // (multi-set plans: a slice of ev_all, set at plan creation)
+        HIP_TRY(pl->set_mem[batch].ev.alloc(ev.size()));
+        b.ev = pl->set_mem[batch].ev.get();
+    }
     HIP_TRY(hipMemcpy(b.ev, ev.data(), ev.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     b.ev_any = n > 0;
     if (pl->multiset) {
@@ -1715,18 +1664,12 @@ static int rebuild_active(jtp_plan *pl, hipStream_t s) {
             pl->esum_oct_host[t * (size_t)pl->n_groups + g] = (free_e || hp.knobs.esum_always) ? 1 : 0;
         }
     }
-    if ((int)fan.size() > pl->cap_fanout) {
-        if (pl->d_fanout) HIP_TRY(hipFree(pl->d_fanout));
-        pl->d_fanout = nullptr;
-        pl->cap_fanout = 0;
-        HIP_TRY(hipMalloc((void **)&pl->d_fanout, fan.size() * sizeof(JtFanout)));
-        pl->cap_fanout = (int)fan.size();
-    }
-    HIP_TRY(hipMemcpyAsync(pl->d_member, pl->member_host.data(), pl->member_host.size(), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(pl->d_act_ids, pl->act_ids_host.data(), pl->act_ids_host.size() * sizeof(uint16_t), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(pl->d_act_n, pl->act_n_host.data(), pl->act_n_host.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    HIP_TRY(hipMemcpyAsync(pl->d_esum_oct, pl->esum_oct_host.data(), pl->esum_oct_host.size(), hipMemcpyHostToDevice, s));
-    if (!fan.empty()) HIP_TRY(hipMemcpyAsync(pl->d_fanout, fan.data(), fan.size() * sizeof(JtFanout), hipMemcpyHostToDevice, s));
+    HIP_TRY(pl->d_fanout.reserve(fan.size()));
+    HIP_TRY(hipMemcpyAsync(pl->d_member.get(), pl->member_host.data(), pl->member_host.size(), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(pl->d_act_ids.get(), pl->act_ids_host.data(), pl->act_ids_host.size() * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(pl->d_act_n.get(), pl->act_n_host.data(), pl->act_n_host.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(pl->d_esum_oct.get(), pl->esum_oct_host.data(), pl->esum_oct_host.size(), hipMemcpyHostToDevice, s));
+    if (!fan.empty()) HIP_TRY(hipMemcpyAsync(pl->d_fanout.get(), fan.data(), fan.size() * sizeof(JtFanout), hipMemcpyHostToDevice, s));
     HIP_TRY(hipStreamSynchronize(s));                    // (the sources are host vectors)
     pl->n_fanout = (int)fan.size();
     pl->act_dirty = false;
@@ -1734,12 +1677,12 @@ static int rebuild_active(jtp_plan *pl, hipStream_t s) {
         JtFlow fl;
         memset(&fl, 0, sizeof fl);
         fl.set_stride = pl->set_stride;
-        fl.oth_off = std::max<int64_t>(hp.msg_doubles, 2);          // (the second half starts here: the pass marks both)
-        hipLaunchKernelGGL(jt_multi_fanout, dim3(pl->n_fanout), dim3(256), 0, s, pl->d_fanout, pl->msg_all, fl);
+        fl.oth_off = pl->half;                                      // (the second half starts here: the pass marks both)
+        hipLaunchKernelGGL(jt_multi_fanout, dim3(pl->n_fanout), dim3(256), 0, s, pl->d_fanout.get(), pl->msg_all.get(), fl);
         HIP_TRY(hipGetLastError());
         // (the marks cover the partial copies of chunks that do not exist, which nobody writes again: set back to their zeros)
         if (pl->d_init[0] || pl->d_init[1])
-            if (int rc = zero_padding(pl, pl->msg_all, pl->n_groups * JT_MSETS, s)) return rc;
+            if (int rc = zero_padding(pl, pl->msg_all.get(), pl->n_groups * JT_MSETS, s)) return rc;
     }
     return JTP_OK;
 }
@@ -1767,35 +1710,35 @@ int jtp_propagate(jtp_plan *pl, int32_t batch_begin, int32_t batch_end) {
             pl->ev.push_back(e);
         }
         const size_t ev_base = prof ? 3 * (size_t)(pl->prof_cursor % pl->prof_steps) : 0;
-        const int64_t half = std::max<int64_t>(hp.msg_doubles, 2);
+        const int64_t half = pl->half;
         for (auto &bb : pl->bufs) bb.epoch++;
         BatchBuffers &b0 = pl->bufs[0];
         JtFlow fl;
         memset(&fl, 0, sizeof fl);
-        fl.sync = pl->sync_all;
-        fl.host_abort = pl->host_abort;
-        fl.cur_off = b0.cur_off(half);
+        fl.sync = pl->sync_all.get();
+        fl.host_abort = pl->host_abort.get();
+        fl.cur_off = cur_half(pl, b0);
         fl.oth_off = half - fl.cur_off;                      // the kernel waits on markers in every launch mode
         fl.dbg = pl->flow_debug;
-        fl.ev = pl->ev_all;
+        fl.ev = pl->ev_all.get();
         fl.set_stride = pl->set_stride;
         fl.ev_stride = pl->ev_stride;
         fl.sync_stride = (uint32_t)hp.sync_words;
         if (pl->act_dirty) {
             if (int rc2 = rebuild_active(pl, s)) return rc2;
         }
-        fl.skip = pl->d_member;
-        fl.act_ids = pl->d_act_ids;
-        fl.act_n = pl->d_act_n;
-        fl.esum_oct = pl->d_esum_oct;
+        fl.skip = pl->d_member.get();
+        fl.act_ids = pl->d_act_ids.get();
+        fl.act_n = pl->d_act_n.get();
+        fl.esum_oct = pl->d_esum_oct.get();
         fl.cap = (uint32_t)(pl->n_groups * JT_MSETS);
         fl.n_tasks = (uint32_t)hp.tasks.size();
         if (pl->esum_dirty) {
             // which groups may sum a vector's elements first on which task (jtp_set_evidence): the fields of ALL tasks in one
             // strided copy, ordered before the launches below on the plan's stream
-            HIP_TRY(hipMemcpy2DAsync(&pl->d_tasks[0].esum_groups, sizeof(JtTask), &hp.tasks[0].esum_groups, sizeof(JtTask), sizeof(uint64_t),
+            HIP_TRY(hipMemcpy2DAsync(&pl->d_tasks.get()[0].esum_groups, sizeof(JtTask), &hp.tasks[0].esum_groups, sizeof(JtTask), sizeof(uint64_t),
                                      hp.tasks.size(), hipMemcpyHostToDevice, s));
-            HIP_TRY(hipMemcpy2DAsync(&pl->d_tasks[0].esum, sizeof(JtTask), &hp.tasks[0].esum, sizeof(JtTask), sizeof(int32_t),
+            HIP_TRY(hipMemcpy2DAsync(&pl->d_tasks.get()[0].esum, sizeof(JtTask), &hp.tasks[0].esum, sizeof(JtTask), sizeof(int32_t),
                                      hp.tasks.size(), hipMemcpyHostToDevice, s));
             HIP_TRY(hipStreamSynchronize(s));                    // (the source is the plan's own task table: pageable)
             pl->esum_dirty = false;
@@ -1822,11 +1765,11 @@ int jtp_propagate(jtp_plan *pl, int32_t batch_begin, int32_t batch_end) {
             // (1-D grid: eight records of group 0, the same eight of group 1, ... - see jt_multi_flow)
             const unsigned grid = (unsigned)((nblocks + 7) / 8) * 8u * (unsigned)pl->n_groups;
             if (hp.dtype == JTP_F32)
-                hipLaunchKernelGGL(jt_multi_flow<float>, dim3(grid), dim3(JT_THREADS), lds, s, pl->d_tasks, pl->d_blocks + blk_off,
-                                   pl->d_itab, (const float *)b0.psi, (float *)b0.bel, pl->msg_all, fl);
+                hipLaunchKernelGGL(jt_multi_flow<float>, dim3(grid), dim3(JT_THREADS), lds, s, pl->d_tasks.get(), pl->d_blocks.get() + blk_off,
+                                   pl->d_itab.get(), (const float *)b0.psi, (float *)b0.bel, pl->msg_all.get(), fl);
             else
-                hipLaunchKernelGGL(jt_multi_flow<double>, dim3(grid), dim3(JT_THREADS), lds, s, pl->d_tasks, pl->d_blocks + blk_off,
-                                   pl->d_itab, (const double *)b0.psi, (double *)b0.bel, pl->msg_all, fl);
+                hipLaunchKernelGGL(jt_multi_flow<double>, dim3(grid), dim3(JT_THREADS), lds, s, pl->d_tasks.get(), pl->d_blocks.get() + blk_off,
+                                   pl->d_itab.get(), (const double *)b0.psi, (double *)b0.bel, pl->msg_all.get(), fl);
         };
         for (const Step &st : (flow ? hp.flow_steps : hp.steps)) {
             if (st.kind != 0) continue;
@@ -1873,14 +1816,14 @@ int jtp_propagate(jtp_plan *pl, int32_t batch_begin, int32_t batch_end) {
         bool mid_done = false;
         if (per_phase) HIP_TRY(hipEventRecord(pl->ev[ev_base + 0], s));
         const bool flow = pl->flow && !per_launch;
-        const int64_t half = std::max<int64_t>(hp.msg_doubles, 2);
+        const int64_t half = pl->half;
         bb.epoch++;
         bb.scale_fresh = false;
         JtFlow fl;
         memset(&fl, 0, sizeof fl);
         fl.sync = bb.sync;
-        fl.host_abort = pl->host_abort;
-        fl.cur_off = bb.cur_off(half);
+        fl.host_abort = pl->host_abort.get();
+        fl.cur_off = cur_half(pl, bb);
         // (a plan that launches per level never waits on entries: it need not mark the other half)
         fl.oth_off = pl->flow ? half - fl.cur_off : -1;
         fl.dbg = pl->flow_debug;
@@ -1917,11 +1860,11 @@ int jtp_propagate(jtp_plan *pl, int32_t batch_begin, int32_t batch_end) {
                 fl.blk_base = (uint32_t)sg.blk_off;
                 fl.ticket_base = ticket_run * (uint32_t)sg.nblocks;
                 if (hp.dtype == JTP_F32)
-                    hipLaunchKernelGGL(KernelTable<float>::get_flow(sg.phase, pl->chain, mixk(hp), pl->marg_tasks), dim3(sg.nblocks), dim3(JT_THREADS), sg.lds_bytes, s, pl->d_tasks,
-                                       pl->d_blocks + sg.blk_off, pl->d_itab, (const float *)bb.psi, (float *)bb.bel, bb.msg, fl);
+                    hipLaunchKernelGGL(KernelTable<float>::get_flow(sg.phase, pl->chain, mixk(hp), pl->marg_tasks), dim3(sg.nblocks), dim3(JT_THREADS), sg.lds_bytes, s, pl->d_tasks.get(),
+                                       pl->d_blocks.get() + sg.blk_off, pl->d_itab.get(), (const float *)bb.psi, (float *)bb.bel, bb.msg, fl);
                 else
-                    hipLaunchKernelGGL(KernelTable<double>::get_flow(sg.phase, pl->chain, mixk(hp), pl->marg_tasks), dim3(sg.nblocks), dim3(JT_THREADS), sg.lds_bytes, s, pl->d_tasks,
-                                       pl->d_blocks + sg.blk_off, pl->d_itab, (const double *)bb.psi, (double *)bb.bel, bb.msg, fl);
+                    hipLaunchKernelGGL(KernelTable<double>::get_flow(sg.phase, pl->chain, mixk(hp), pl->marg_tasks), dim3(sg.nblocks), dim3(JT_THREADS), sg.lds_bytes, s, pl->d_tasks.get(),
+                                       pl->d_blocks.get() + sg.blk_off, pl->d_itab.get(), (const double *)bb.psi, (double *)bb.bel, bb.msg, fl);
             } else if (st.kind == 0) {
                 const Launch &L = hp.launches[st.first];
                 if (per_phase && !mid_done && L.phase == 1) {
@@ -1930,11 +1873,11 @@ int jtp_propagate(jtp_plan *pl, int32_t batch_begin, int32_t batch_end) {
                 }
                 if (per_launch) HIP_TRY(hipEventRecord(pl->ev[ev_base + 2 * st.first], s));
                 fl.blk_base = (uint32_t)L.blk_off;
-                launch_variant(pl, L.variant, L.nblocks, L.lds_bytes, s, pl->d_tasks, pl->d_blocks + L.blk_off, pl->d_itab, bb.psi, bb.bel, bb.msg, fl);
+                launch_variant(pl, L.variant, L.nblocks, L.lds_bytes, s, pl->d_tasks.get(), pl->d_blocks.get() + L.blk_off, pl->d_itab.get(), bb.psi, bb.bel, bb.msg, fl);
                 if (per_launch) HIP_TRY(hipEventRecord(pl->ev[ev_base + 2 * st.first + 1], s));
             } else if (st.kind == 2) {
                 // (JTP_SCALED: the messages the level before has just produced, a workgroup each)
-                hipLaunchKernelGGL(jt_rescale_level, dim3((unsigned)st.count), dim3(256), 0, s, pl->d_rescale + st.first, bb.msg + fl.cur_off, bb.exps);
+                hipLaunchKernelGGL(jt_rescale_level, dim3((unsigned)st.count), dim3(256), 0, s, pl->d_rescale.get() + st.first, bb.msg + fl.cur_off, bb.exps);
             } else if (pl->fake_comm == 2) {
                 // loop-back: the step's sends and receives as one RCCL group addressed to this rank itself (RCCL pairs the k-th
                 // send to a peer with the k-th receive from it: a receive without a send of its own takes this rank's first
@@ -1947,7 +1890,7 @@ int jtp_propagate(jtp_plan *pl, int32_t batch_begin, int32_t batch_end) {
                 for (int i = st.first; i < st.first + st.count; ++i) most = std::max(most, hp.comm[i].count);
                 const int rc2 = ensure_stage(pl, (size_t)most * 8 * 2);
                 if (rc2) return rc2;
-                double *spare = (double *)pl->stage;
+                double *spare = (double *)pl->stage.get();
                 NCCL_TRY(rccl::GroupStart());
                 for (size_t k = 0; k < n; ++k) {
                     const CommOp *sd = k < sends.size() ? sends[k] : nullptr, *rv = k < recvs.size() ? recvs[k] : nullptr;
@@ -2028,66 +1971,67 @@ int jtp_get_belief(jtp_plan *pl, int32_t batch, int32_t node, void *host, int32_
     if (node < hp.n_cliques) {
         if (!(hp.pn[node].owner == hp.rank || hp.pn[node].owner == hp.n_ranks)) return set_err(JTP_EINVAL, "clique %d belongs to rank %d", node, hp.pn[node].owner);
         const JtPackDesc &d = hp.pack[node];
+        const bool unit = hp.pn[node].unit;
+        const bool direct = pl->multiset || unit;
+        // What the first call needs is built into locals and moved into the plan once ALL of it is there: a call that fails leaves
+        // the plan as it found it.
+        //  - a unit clique keeps no belief table either: formed now, into a scratch arena laid out as its table would be;
+        //  - multi-set plans and unit cliques keep no belief tables: this clique's belief for this evidence set is formed now, from
+        //    the shared table and the set's final messages (computation.py:216-224), by a task of its own.
+        DeviceBuf<char> scratch(&pl->mem);
+        jtp_plan::BeliefTask fresh(&pl->mem);
+        if (unit && !pl->unit_scratch) HIP_TRY(scratch.alloc((size_t)hp.scratch_elems * pl->esize));
+        if (direct && pl->belief_tasks.size() < hp.pn.size()) pl->belief_tasks.resize(hp.pn.size());
+        if (direct && !pl->belief_tasks[node].d_task) {
+            JtTask tk;
+            std::vector<int32_t> itab;
+            std::vector<JtBlock> blocks;
+            std::string err;
+            rc = jtp_plan_belief_task(hp, node, tk, itab, blocks, err);
+            if (rc) return set_err(rc, "%s", err.c_str());
+            HIP_TRY(fresh.d_task.upload(&tk, 1));
+            HIP_TRY(fresh.d_blk.upload(blocks));
+            HIP_TRY(fresh.d_tab.upload(itab, 1));
+            fresh.h_task = tk;
+            fresh.nblocks = (int)blocks.size();
+            fresh.lds = tk.lds_bytes;
+        }
         rc = ensure_stage(pl, (size_t)d.host_elems * hsz);
         if (rc) return rc;
-        const bool unit = hp.pn[node].unit;
-        void *bel_src = b.bel;
-        if (unit) {
-            // a unit clique keeps no belief table either: formed now, into a scratch arena laid out as its table would be
-            if (!pl->unit_scratch) {
-                HIP_TRY(hipMalloc(&pl->unit_scratch, (size_t)hp.scratch_elems * pl->esize));
-                HIP_TRY(hipMemsetAsync(pl->unit_scratch, 0, (size_t)hp.scratch_elems * pl->esize, s));
-            }
-            bel_src = pl->unit_scratch;
+        if (scratch) {
+            pl->unit_scratch = std::move(scratch);
+            HIP_TRY(hipMemsetAsync(pl->unit_scratch.get(), 0, pl->unit_scratch.bytes(), s));
         }
-        if (pl->multiset || unit) {
-            // no belief tables are kept: form this clique's belief for this evidence set now, from the shared
-            // table and the set's final messages (computation.py:216-224), into the scratch arena
-            if (pl->belief_tasks.size() < hp.pn.size()) pl->belief_tasks.resize(hp.pn.size());
+        if (fresh.d_task) pl->belief_tasks[node] = std::move(fresh);
+        void *bel_src = unit ? (void *)pl->unit_scratch.get() : b.bel;
+        if (direct) {
             jtp_plan::BeliefTask &bt = pl->belief_tasks[node];
-            if (!bt.d_task) {
-                JtTask tk;
-                std::vector<int32_t> itab;
-                std::vector<JtBlock> blocks;
-                std::string err;
-                rc = jtp_plan_belief_task(hp, node, tk, itab, blocks, err);
-                if (rc) return set_err(rc, "%s", err.c_str());
-                HIP_TRY(hipMalloc((void **)&bt.d_task, sizeof(JtTask)));
-                HIP_TRY(hipMalloc((void **)&bt.d_blk, blocks.size() * sizeof(JtBlock)));
-                HIP_TRY(hipMalloc((void **)&bt.d_tab, std::max<size_t>(itab.size(), 1) * sizeof(int32_t)));
-                HIP_TRY(hipMemcpy(bt.d_task, &tk, sizeof tk, hipMemcpyHostToDevice));
-                bt.h_task = tk;
-                HIP_TRY(hipMemcpy(bt.d_blk, blocks.data(), blocks.size() * sizeof(JtBlock), hipMemcpyHostToDevice));
-                if (!itab.empty()) HIP_TRY(hipMemcpy(bt.d_tab, itab.data(), itab.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-                bt.nblocks = (int)blocks.size();
-                bt.lds = tk.lds_bytes;
-            }
             if (pl->multiset && pl->set0) {              // (which inputs come from the evidence-free set's arena depends on the set)
                 JtTask patched = bt.h_task;
                 readout_redirect(pl, batch, patched);
                 HIP_TRY(hipStreamSynchronize(s));        // (an earlier read-out's kernel may still read the record)
-                HIP_TRY(hipMemcpy(bt.d_task, &patched, sizeof patched, hipMemcpyHostToDevice));
+                HIP_TRY(hipMemcpy(bt.d_task.get(), &patched, sizeof patched, hipMemcpyHostToDevice));
             }
             JtFlow one;
             memset(&one, 0, sizeof one);
-            one.cur_off = b.cur_off(std::max<int64_t>(hp.msg_doubles, 2));
+            one.cur_off = cur_half(pl, b);
             one.oth_off = -1;
             one.ev = b.ev_any || pl->multiset ? b.ev : nullptr;
             one.fix_shift = b.fix_shift(one.cur_off);
-            HIP_TRY(raise_lds(hp.dtype == JTP_F32 ? (const void *)KernelTable<float>::get(JT_K_SINGLE, mixk(hp)) : (const void *)KernelTable<double>::get(JT_K_SINGLE, mixk(hp)), bt.lds));
-            launch_variant(pl, JT_K_SINGLE, bt.nblocks, bt.lds, s, bt.d_task, bt.d_blk, bt.d_tab, b.psi, bel_src, b.msg, one);
+            rc = launch_readout(pl, JT_K_SINGLE, bt.nblocks, bt.lds, s, bt.d_task.get(), bt.d_blk.get(), bt.d_tab.get(), b.psi, bel_src, b.msg, one);
+            if (rc) return rc;
             HIP_TRY(hipGetLastError());
         }
-        const int grid = (int)std::min<int64_t>((d.host_elems + 255) / 256, 4096);
+        const int grid = grid_1d(d.host_elems);
         if (hp.dtype == JTP_F32) {
-            if (host_dtype == JTP_F32) hipLaunchKernelGGL((jt_unpack<float, float>), dim3(grid), dim3(256), 0, s, d, (const float *)bel_src, (float *)pl->stage);
-            else hipLaunchKernelGGL((jt_unpack<float, double>), dim3(grid), dim3(256), 0, s, d, (const float *)bel_src, (double *)pl->stage);
+            if (host_dtype == JTP_F32) hipLaunchKernelGGL((jt_unpack<float, float>), dim3(grid), dim3(256), 0, s, d, (const float *)bel_src, (float *)pl->stage.get());
+            else hipLaunchKernelGGL((jt_unpack<float, double>), dim3(grid), dim3(256), 0, s, d, (const float *)bel_src, (double *)pl->stage.get());
         } else {
-            if (host_dtype == JTP_F32) hipLaunchKernelGGL((jt_unpack<double, float>), dim3(grid), dim3(256), 0, s, d, (const double *)bel_src, (float *)pl->stage);
-            else hipLaunchKernelGGL((jt_unpack<double, double>), dim3(grid), dim3(256), 0, s, d, (const double *)bel_src, (double *)pl->stage);
+            if (host_dtype == JTP_F32) hipLaunchKernelGGL((jt_unpack<double, float>), dim3(grid), dim3(256), 0, s, d, (const double *)bel_src, (float *)pl->stage.get());
+            else hipLaunchKernelGGL((jt_unpack<double, double>), dim3(grid), dim3(256), 0, s, d, (const double *)bel_src, (double *)pl->stage.get());
         }
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(host, pl->stage, (size_t)d.host_elems * hsz, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(host, pl->stage.get(), (size_t)d.host_elems * hsz, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         return check_flow(pl, batch);
     }
@@ -2095,38 +2039,30 @@ int jtp_get_belief(jtp_plan *pl, int32_t batch, int32_t node, void *host, int32_
     if (si < 0) return set_err(JTP_EINVAL, "separator node %d is not part of the tree", node);
     const PSep &sp = hp.ps[si];
     if (sp.up_off < 0) return set_err(JTP_EINVAL, "separator node %d is not held by rank %d", node, hp.rank);
-    JtPackDesc d;
-    memset(&d, 0, sizeof d);
-    d.nvars = (int)hp.node_vars[node].size();
-    d.nbits = sp.nbits;
-    int64_t stride = 1;
-    for (int i = d.nvars - 1; i >= 0; --i) {
-        const int v = hp.node_vars[node][i];
+    std::vector<int> pos, nb;                               // the separator's layout in the node's host axis order
+    for (int v : hp.node_vars[node]) {
         int j = 0;
         while (sp.vars[j] != v) ++j;
-        d.pos[i] = (uint8_t)sp.pos[j];
-        d.nb[i] = (uint8_t)sp.nb[j];
-        d.card[i] = hp.card[v];
-        d.hstride[i] = stride;
-        stride *= hp.card[v];
+        pos.push_back(sp.pos[j]);
+        nb.push_back(sp.nb[j]);
     }
-    d.host_elems = stride;
-    bitfield_desc(d);
+    const JtPackDesc d = bitfield_desc(hp, hp.node_vars[node], pos.data(), nb.data(), sp.nbits);
+    const int64_t stride = d.host_elems;
     rc = ensure_stage(pl, (size_t)stride * hsz);
     if (rc) return rc;
-    const int grid = (int)std::min<int64_t>((stride + 255) / 256, 4096);
+    const int grid = grid_1d(stride);
     const int64_t pstride = (int64_t)1 << sp.nbits;
-    const double *cur = b.msg + b.cur_off(std::max<int64_t>(hp.msg_doubles, 2));      // the half the last propagate wrote
+    const double *cur = b.msg + cur_half(pl, b);            // the half the last propagate wrote
     const double *cur_up = cur;
     if (pl->multiset && pl->set0 && !pl->member_host.empty() && sp.child >= 0 && hp.pn[sp.child].collect_task >= 0 &&
         !pl->member_host[(size_t)hp.pn[sp.child].collect_task * ((size_t)pl->n_groups * JT_MSETS) + (size_t)(pl->set0 + batch)])
-        cur_up = pl->msg_all + b.cur_off(std::max<int64_t>(hp.msg_doubles, 2));       // (readout_redirect: the evidence-free set's upward message)
+        cur_up = pl->msg_all.get() + cur_half(pl, b);       // (readout_redirect: the evidence-free set's upward message)
     if (host_dtype == JTP_F32)
-        hipLaunchKernelGGL((jt_msg_unpack<float>), dim3(grid), dim3(256), 0, s, d, cur_up + sp.up_roff, sp.up_rnpart, cur + sp.dn_roff, sp.dn_rnpart, pstride, (float *)pl->stage);
+        hipLaunchKernelGGL((jt_msg_unpack<float>), dim3(grid), dim3(256), 0, s, d, cur_up + sp.up_roff, sp.up_rnpart, cur + sp.dn_roff, sp.dn_rnpart, pstride, (float *)pl->stage.get());
     else
-        hipLaunchKernelGGL((jt_msg_unpack<double>), dim3(grid), dim3(256), 0, s, d, cur_up + sp.up_roff, sp.up_rnpart, cur + sp.dn_roff, sp.dn_rnpart, pstride, (double *)pl->stage);
+        hipLaunchKernelGGL((jt_msg_unpack<double>), dim3(grid), dim3(256), 0, s, d, cur_up + sp.up_roff, sp.up_rnpart, cur + sp.dn_roff, sp.dn_rnpart, pstride, (double *)pl->stage.get());
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(host, pl->stage, (size_t)stride * hsz, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(host, pl->stage.get(), (size_t)stride * hsz, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     return check_flow(pl, batch);
 }
@@ -2180,9 +2116,8 @@ int jtp_get_marginals(jtp_plan *pl, int32_t batch, int32_t n, const int32_t *cli
     MargBatch *mb = nullptr;
     for (size_t i = 0; i < pl->marg_cache.size(); ++i)
         if (pl->marg_cache[i]->key == key) {                // most recently used last
-            mb = pl->marg_cache[i];
-            pl->marg_cache.erase(pl->marg_cache.begin() + i);
-            pl->marg_cache.push_back(mb);
+            std::rotate(pl->marg_cache.begin() + i, pl->marg_cache.begin() + i + 1, pl->marg_cache.end());
+            mb = pl->marg_cache.back().get();
             break;
         }
     if (!mb) {
@@ -2252,24 +2187,15 @@ int jtp_get_marginals(jtp_plan *pl, int32_t batch, int32_t n, const int32_t *cli
                 tk.msg[JT_MAX_IN + j].off = scratch_doubles;
                 JtMargDesc md;
                 memset(&md, 0, sizeof md);
-                md.d.nvars = n_out;
-                md.d.nbits = out_bits[j];
-                int64_t stride = 1;
                 int bit = 0;
-                std::vector<int> pos(n_out);
+                std::vector<int> pos(n_out), nb(n_out);
                 for (int a = n_out - 1; a >= 0; --a) {          // last requested variable = lowest bits
                     pos[a] = bit;
-                    bit += hp.vbits[ov[a]];
+                    nb[a] = hp.vbits[ov[a]];
+                    bit += nb[a];
                 }
-                for (int a = n_out - 1; a >= 0; --a) {
-                    md.d.pos[a] = (uint8_t)pos[a];
-                    md.d.nb[a] = (uint8_t)hp.vbits[ov[a]];
-                    md.d.card[a] = hp.card[ov[a]];
-                    md.d.hstride[a] = stride;
-                    stride *= hp.card[ov[a]];
-                }
-                md.d.host_elems = stride;
-                bitfield_desc(md.d);
+                md.d = bitfield_desc(hp, ov, pos.data(), nb.data(), out_bits[j]);
+                const int64_t stride = md.d.host_elems;
                 md.src_off = scratch_doubles;
                 md.pstride = (int64_t)1 << out_bits[j];
                 md.npart = npart[j];
@@ -2291,7 +2217,9 @@ int jtp_get_marginals(jtp_plan *pl, int32_t batch, int32_t n, const int32_t *cli
         int n_lean_blocks = 0, lean_lds = 0;
         for (const JtBlock &bk : ublocks)
             if (tasks[bk.task].lean_off > 0) ++n_lean_blocks, lean_lds = std::max(lean_lds, tasks[bk.task].lds_bytes);
-        mb = new MargBatch();
+        // (the tables of the list are complete before the plan sees them: a failure below leaves the cache as it was)
+        std::unique_ptr<MargBatch> made(new MargBatch(&pl->mem));
+        mb = made.get();
         mb->lean_nblocks = n_lean_blocks;
         mb->lean_lds = lean_lds;
         if (pl->multiset && pl->set0) mb->h_tasks = tasks;
@@ -2307,18 +2235,14 @@ int jtp_get_marginals(jtp_plan *pl, int32_t batch, int32_t n, const int32_t *cli
         int64_t biggest = 1;
         for (int64_t e : elems) biggest = std::max(biggest, e);
         mb->max_grid_x = (int)std::min<int64_t>((biggest + 255) / 256, 64);
-        hipError_t e = hipMalloc((void **)&mb->d_tasks, tasks.size() * sizeof(JtTask));
-        if (e == hipSuccess) e = hipMalloc((void **)&mb->d_blocks, blocks.size() * sizeof(JtBlock));
-        if (e == hipSuccess) e = hipMalloc((void **)&mb->d_itab, std::max<size_t>(itab.size(), 1) * sizeof(int32_t));
-        if (e == hipSuccess) e = hipMalloc((void **)&mb->d_descs, descs.size() * sizeof(JtMargDesc));
-        if (e == hipSuccess) e = hipMalloc((void **)&mb->scratch, (size_t)std::max<int64_t>(scratch_doubles, 1) * 8);
-        if (e == hipSuccess) e = hipMalloc((void **)&mb->stage, (size_t)std::max<int64_t>(total_out, 1) * 8);
-        if (e == hipSuccess) e = hipMemcpy(mb->d_tasks, tasks.data(), tasks.size() * sizeof(JtTask), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(mb->d_blocks, blocks.data(), blocks.size() * sizeof(JtBlock), hipMemcpyHostToDevice);
-        if (e == hipSuccess && !itab.empty()) e = hipMemcpy(mb->d_itab, itab.data(), itab.size() * sizeof(int32_t), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(mb->d_descs, descs.data(), descs.size() * sizeof(JtMargDesc), hipMemcpyHostToDevice);
+        HIP_TRY(mb->d_tasks.upload(tasks));
+        HIP_TRY(mb->d_blocks.upload(blocks));
+        HIP_TRY(mb->d_itab.upload(itab, 1));
+        HIP_TRY(mb->d_descs.upload(descs));
+        HIP_TRY(mb->scratch.alloc((size_t)std::max<int64_t>(scratch_doubles, 1)));
+        HIP_TRY(mb->stage.alloc((size_t)std::max<int64_t>(total_out, 1)));
         // the plan's own list: where the folded tasks of the propagate leave these marginals
-        if (e == hipSuccess && !hp.folded.empty() && key == hp.fold_key && !pl->multiset) {
+        if (!hp.folded.empty() && key == hp.fold_key && !pl->multiset) {
             bool all = true;
             std::vector<JtMargDesc> fd = descs;
             for (int i = 0; i < n; ++i) {
@@ -2335,40 +2259,27 @@ int jtp_get_marginals(jtp_plan *pl, int32_t batch, int32_t n, const int32_t *cli
                 fd[i].in_arena = 1;
             }
             if (all) {
-                e = hipMalloc((void **)&mb->d_descs_fold, fd.size() * sizeof(JtMargDesc));
-                if (e == hipSuccess) e = hipMemcpy(mb->d_descs_fold, fd.data(), fd.size() * sizeof(JtMargDesc), hipMemcpyHostToDevice);
-                mb->folded = e == hipSuccess;
+                HIP_TRY(mb->d_descs_fold.upload(fd));
+                mb->folded = true;
             }
         }
-        if (e != hipSuccess) {
-            mb->release();
-            delete mb;
-            return set_err(e == hipErrorOutOfMemory ? JTP_ENOMEM : JTP_EHIP, "marginal tables: %s", hipGetErrorString(e));
-        }
-        if (pl->marg_cache.size() >= 32) {                  // a model asks for a few lists (and Z); keep the last used
-            pl->marg_cache.front()->release();
-            delete pl->marg_cache.front();
-            pl->marg_cache.erase(pl->marg_cache.begin());
-        }
-        pl->marg_cache.push_back(mb);
+        if (pl->marg_cache.size() >= 32) pl->marg_cache.erase(pl->marg_cache.begin());      // a model asks for a few lists (and Z); keep the last used
+        pl->marg_cache.push_back(std::move(made));
     }
     if (!mb->h_tasks.empty()) {                          // (multi-set plans with active lists: readout_redirect, per evidence set)
         std::vector<JtTask> patched = mb->h_tasks;
         for (JtTask &tk : patched) readout_redirect(pl, batch, tk);
         HIP_TRY(hipStreamSynchronize(s));
-        HIP_TRY(hipMemcpy(mb->d_tasks, patched.data(), patched.size() * sizeof(JtTask), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(mb->d_tasks.get(), patched.data(), patched.size() * sizeof(JtTask), hipMemcpyHostToDevice));
     }
-    // the kernels that are actually launched below must be allowed this much dynamic LDS
-    if (mb->nblocks > 0)
-        HIP_TRY(raise_lds(hp.dtype == JTP_F32 ? (const void *)KernelTable<float>::get(JT_K_MARGINALS, mixk(hp)) : (const void *)KernelTable<double>::get(JT_K_MARGINALS, mixk(hp)), mb->lds));
-    if (mb->unit_nblocks > 0)
-        HIP_TRY(raise_lds(hp.dtype == JTP_F32 ? (const void *)KernelTable<float>::get(JT_K_SINGLE, mixk(hp)) : (const void *)KernelTable<double>::get(JT_K_SINGLE, mixk(hp)), mb->unit_lds));
     JtFlow plain;
     memset(&plain, 0, sizeof plain);
     plain.oth_off = -1;
     // marginalise the BELIEF tables: each is the "potential" argument of a childless collect
-    if (mb->nblocks > 0)
-        launch_variant(pl, JT_K_MARGINALS, mb->nblocks, mb->lds, s, mb->d_tasks, mb->d_blocks, mb->d_itab, b.bel, b.bel, mb->scratch, plain);
+    if (mb->nblocks > 0) {
+        rc = launch_readout(pl, JT_K_MARGINALS, mb->nblocks, mb->lds, s, mb->d_tasks.get(), mb->d_blocks.get(), mb->d_itab.get(), b.bel, b.bel, mb->scratch.get(), plain);
+        if (rc) return rc;
+    }
     // Marginals the propagate formed itself (fold_marginals): valid when the last propagate of this evidence set ran them - a dataflow
     // launch whose distribute segment is jt_propagate_flow, or one launch per level - and the set observes nothing (a clique that hosts
     // an observed variable has no lean pass).  Then only the belief-table requests are computed here.
@@ -2385,30 +2296,32 @@ int jtp_get_marginals(jtp_plan *pl, int32_t batch, int32_t n, const int32_t *cli
         // cliques that keep no belief table (multi-set plans: all; else the unit cliques): psi * (the incoming tables)
         // marginalised directly - inputs from the set's message arena (and the fixed arena), outputs into the request list's
         // scratch buffer (JtFlow::out_shift)
-        plain.cur_off = b.cur_off(std::max<int64_t>(hp.msg_doubles, 2));
+        plain.cur_off = cur_half(pl, b);
         plain.ev = b.ev_any || pl->multiset ? b.ev : nullptr;
         plain.fix_shift = b.fix_shift(plain.cur_off);
-        plain.out_shift = (int64_t)(((intptr_t)mb->scratch - (intptr_t)(b.msg + plain.cur_off)) / 8);
+        plain.out_shift = (int64_t)(((intptr_t)mb->scratch.get() - (intptr_t)(b.msg + plain.cur_off)) / 8);
         // (round 6) the tasks with a lean record through jt_lean_single while the evidence set observes nothing
         const int n_lean = plain.ev == nullptr ? mb->lean_nblocks : 0;
         if (n_lean > 0) {
-            HIP_TRY(raise_lds(hp.dtype == JTP_F32 ? (const void *)KernelTable<float>::get(JT_K_LEAN_SINGLE, 0) : (const void *)KernelTable<double>::get(JT_K_LEAN_SINGLE, 0), mb->lean_lds));
-            launch_variant(pl, JT_K_LEAN_SINGLE, n_lean, mb->lean_lds, s, mb->d_tasks, mb->d_blocks + mb->nblocks, mb->d_itab, b.psi, b.bel, b.msg, plain);
+            rc = launch_readout(pl, JT_K_LEAN_SINGLE, n_lean, mb->lean_lds, s, mb->d_tasks.get(), mb->d_blocks.get() + mb->nblocks, mb->d_itab.get(), b.psi, b.bel, b.msg, plain);
+            if (rc) return rc;
         }
-        if (mb->unit_nblocks > n_lean)
-            launch_variant(pl, JT_K_SINGLE, mb->unit_nblocks - n_lean, mb->unit_lds, s, mb->d_tasks, mb->d_blocks + mb->nblocks + n_lean, mb->d_itab, b.psi, b.bel, b.msg, plain);
+        if (mb->unit_nblocks > n_lean) {
+            rc = launch_readout(pl, JT_K_SINGLE, mb->unit_nblocks - n_lean, mb->unit_lds, s, mb->d_tasks.get(), mb->d_blocks.get() + mb->nblocks + n_lean, mb->d_itab.get(), b.psi, b.bel, b.msg, plain);
+            if (rc) return rc;
+        }
     }
-    hipLaunchKernelGGL(jt_marg_unpack, dim3(mb->max_grid_x, mb->n), dim3(256), 0, s, use_fold ? mb->d_descs_fold : mb->d_descs, mb->scratch, mb->stage,
-                       (const double *)(b.msg + b.cur_off(std::max<int64_t>(hp.msg_doubles, 2))));
+    hipLaunchKernelGGL(jt_marg_unpack, dim3(mb->max_grid_x, mb->n), dim3(256), 0, s, use_fold ? mb->d_descs_fold.get() : mb->d_descs.get(), mb->scratch.get(), mb->stage.get(),
+                       (const double *)(b.msg + cur_half(pl, b)));
     HIP_TRY(hipGetLastError());
     bool packed = true;
     for (int i = 0; i < n; ++i) packed = packed && out_off[i + 1] - out_off[i] == mb->elems[i];
     if (packed) {
-        HIP_TRY(hipMemcpyAsync(host + out_off[0], mb->stage, (size_t)mb->total_out * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(host + out_off[0], mb->stage.get(), (size_t)mb->total_out * 8, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
     } else {
         std::vector<double> tmp((size_t)mb->total_out);
-        HIP_TRY(hipMemcpyAsync(tmp.data(), mb->stage, (size_t)mb->total_out * 8, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(tmp.data(), mb->stage.get(), (size_t)mb->total_out * 8, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
         int64_t at = 0;
         for (int i = 0; i < n; ++i) {
@@ -2530,6 +2443,10 @@ int jtp_sample(jtp_plan *pl, int32_t batch, int32_t n_samples, uint64_t seed, in
     rc = settle(pl, batch);
     if (rc) return rc;
     hipStream_t s = pl->streams[batch % pl->streams.size()];
+    // (first call: the records and the failure report are built into locals and moved into the plan once everything the call
+    //  allocates is there - a call that fails leaves the plan as it found it)
+    DeviceBuf<JtSample> recs_dev(&pl->mem);
+    DeviceBuf<unsigned long long> fail_dev(&pl->mem);
     if (!pl->d_sample) {
         std::vector<JtSample> recs(hp.sample.size());
         for (size_t i = 0; i < recs.size(); ++i) {
@@ -2559,40 +2476,36 @@ int jtp_sample(jtp_plan *pl, int32_t batch, int32_t n_samples, uint64_t seed, in
                 if (j >= r.nK) sv.radix = radix, radix *= (uint32_t)sv.card;
             }
         }
-        HIP_TRY(hipMalloc((void **)&pl->d_sample, std::max<size_t>(recs.size(), 1) * sizeof(JtSample)));
-        HIP_TRY(hipMemcpy(pl->d_sample, recs.data(), recs.size() * sizeof(JtSample), hipMemcpyHostToDevice));
+        HIP_TRY(recs_dev.upload(recs, 1));
     }
+    if (!pl->d_sample_fail) HIP_TRY(fail_dev.alloc(2));
     // samples go in chunks through one buffer of state rows (at most 64 MiB of them, 256 .. 65536 rows): the grid stays within
     // limits whatever n_samples is, and there is one copy back per chunk
     const size_t chunk = std::min<size_t>((size_t)n_samples, std::max<size_t>(256, std::min<size_t>(65536, ((size_t)16 << 20) / (size_t)n_vars)));
-    if (pl->sample_cap < chunk) {
-        if (pl->sample_states) (void)hipFree(pl->sample_states);
-        pl->sample_states = nullptr;
-        pl->sample_cap = 0;
-        if (hipMalloc((void **)&pl->sample_states, chunk * (size_t)n_vars * sizeof(int32_t)) != hipSuccess)
-            return set_err(JTP_ENOMEM, "jtp_sample: cannot allocate %zu state rows of %d variables", chunk, n_vars);
-        pl->sample_cap = chunk;
-    }
-    if (!pl->d_sample_fail) HIP_TRY(hipMalloc((void **)&pl->d_sample_fail, 2 * sizeof(unsigned long long)));
-    HIP_TRY(hipMemsetAsync(pl->d_sample_fail, 0, sizeof(unsigned long long), s));
-    HIP_TRY(hipMemsetAsync(pl->d_sample_fail + 1, 0xff, sizeof(unsigned long long), s));
+    HIP_TRY(pl->sample_states.reserve(chunk * (size_t)n_vars));
+    if (recs_dev) pl->d_sample = std::move(recs_dev);
+    if (fail_dev) pl->d_sample_fail = std::move(fail_dev);
+    int32_t *rows = pl->sample_states.get();
+    unsigned long long *dfail = pl->d_sample_fail.get();
+    HIP_TRY(hipMemsetAsync(dfail, 0, sizeof(unsigned long long), s));
+    HIP_TRY(hipMemsetAsync(dfail + 1, 0xff, sizeof(unsigned long long), s));
     for (size_t at = 0; at < (size_t)n_samples; at += chunk) {
         const size_t cnt = std::min(chunk, (size_t)n_samples - at);
-        HIP_TRY(hipMemsetAsync(pl->sample_states, 0xff, cnt * (size_t)n_vars * sizeof(int32_t), s));      // (-1: nothing drawn yet)
+        HIP_TRY(hipMemsetAsync(rows, 0xff, cnt * (size_t)n_vars * sizeof(int32_t), s));      // (-1: nothing drawn yet)
         for (const std::vector<int> &level : hp.sample_depths)
             for (size_t y0 = 0; y0 < level.size(); y0 += 65535) {                                         // (records of a depth are consecutive)
                 const dim3 grid((unsigned)((cnt + 3) / 4), (unsigned)std::min<size_t>(65535, level.size() - y0));
                 if (hp.dtype == JTP_F32)
-                    hipLaunchKernelGGL(jt_sample_level<float>, grid, dim3(256), 0, s, pl->d_sample + level[0] + y0, (const float *)b.bel, pl->sample_states, n_vars, (int)cnt, (uint64_t)at, seed, pl->d_sample_fail);
+                    hipLaunchKernelGGL(jt_sample_level<float>, grid, dim3(256), 0, s, pl->d_sample.get() + level[0] + y0, (const float *)b.bel, rows, n_vars, (int)cnt, (uint64_t)at, seed, dfail);
                 else
-                    hipLaunchKernelGGL(jt_sample_level<double>, grid, dim3(256), 0, s, pl->d_sample + level[0] + y0, (const double *)b.bel, pl->sample_states, n_vars, (int)cnt, (uint64_t)at, seed, pl->d_sample_fail);
+                    hipLaunchKernelGGL(jt_sample_level<double>, grid, dim3(256), 0, s, pl->d_sample.get() + level[0] + y0, (const double *)b.bel, rows, n_vars, (int)cnt, (uint64_t)at, seed, dfail);
             }
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(states + at * (size_t)n_vars, pl->sample_states, cnt * (size_t)n_vars * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(states + at * (size_t)n_vars, rows, cnt * (size_t)n_vars * sizeof(int32_t), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));                // (the buffer is the next chunk's)
     }
     unsigned long long fail[2] = {0, 0};
-    HIP_TRY(hipMemcpyAsync(fail, pl->d_sample_fail, sizeof fail, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(fail, dfail, sizeof fail, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     rc = check_flow(pl, batch);
     if (rc) return rc;
@@ -2883,11 +2796,12 @@ int jtp_comm_info(int32_t *n_ranks, int32_t *rank, int32_t *device) {
 int jtp_comm_selftest(int32_t n) {
     if (!rccl::comm) return set_err(JTP_ECOMM, "communicator not initialised");
     if (n <= 0) return set_err(JTP_EINVAL, "n must be positive");
-    double *a = nullptr, *b = nullptr;
+    DeviceBuf<double> abuf, bbuf;
+    HIP_TRY(abuf.alloc((size_t)n));
+    HIP_TRY(bbuf.alloc((size_t)n));
+    double *a = abuf.get(), *b = bbuf.get();
     hipStream_t s;
     HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    HIP_TRY(hipMalloc((void **)&a, (size_t)n * 8));
-    HIP_TRY(hipMalloc((void **)&b, (size_t)n * 8));
     std::vector<double> h(n), back(n, -1.0);
     for (int i = 0; i < n; ++i) h[i] = 0.5 * i + 1.0;
     HIP_TRY(hipMemcpyAsync(a, h.data(), (size_t)n * 8, hipMemcpyHostToDevice, s));
@@ -2898,8 +2812,6 @@ int jtp_comm_selftest(int32_t n) {
     NCCL_TRY(rccl::GroupEnd());
     HIP_TRY(hipMemcpyAsync(back.data(), b, (size_t)n * 8, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    (void)hipFree(a);
-    (void)hipFree(b);
     (void)hipStreamDestroy(s);
     for (int i = 0; i < n; ++i)
         if (back[i] != h[i]) return set_err(JTP_ECOMM, "self send/recv mismatch at %d: %g vs %g", i, back[i], h[i]);

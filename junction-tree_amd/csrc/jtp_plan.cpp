@@ -761,6 +761,7 @@ PlanKnobs jtp_read_knobs() {
     k.fold = geti("JTP_FOLD", -1);
     if (k.fold == 0) k.no_fold = 1;
     k.fold_slots = geti("JTP_FOLD_SLOTS", 1024);
+    k.fail_alloc = std::max(0, geti("JTP_FAIL_ALLOC", 0));
     return k;
 }
 

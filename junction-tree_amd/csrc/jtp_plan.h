@@ -206,6 +206,7 @@ struct PlanKnobs {
     int marg_group = JT_MAX_OUT;                                    // JTP_MARG_GROUP: marginals of one belief table formed by one pass over it (1: a pass each, round 3)
     int marg_block_log2 = 0;                                        // JTP_MARG_BLOCK_LOG2: log2 of the elements per workgroup of a marginal pass (0: the 64 rows a workgroup can hold)
     int merge_phases = -1;                                          // JTP_MERGE_PHASES: 1 / 0 = both phases in one dataflow launch / never; -1: where messages are small
+    int fail_alloc = 0;                                             // JTP_FAIL_ALLOC: test hook - the N-th device allocation of jtp_plan_create reports out of memory (0: off)
 };
 PlanKnobs jtp_read_knobs();
 

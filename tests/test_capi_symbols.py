@@ -34,7 +34,16 @@ def test_struct_sizes_match_header():
     assert lib.jtp_kernel_name(_capi.N_VARIANTS) is None
 
 
+def live_bytes():
+    dev, pin = ctypes.c_int64(-1), ctypes.c_int64(-1)
+    assert _capi.lib().jtp_debug_live_bytes(ctypes.byref(dev), ctypes.byref(pin)) == _capi.JTP_OK
+    return dev.value, pin.value
+
+
 def test_plan_only_needs_no_gpu_and_device_plans_fail_loudly_without_one():
+    without_device = _capi.device_count() == 0
+    if without_device:
+        assert live_bytes() == (0, 0)
     plan = engine.Plan([0, (2, [1])], [[1, 2], [2, 3], [2]], {1: 2, 2: 3, 3: 2}, plan_only=True)
     d = plan.describe()
     assert d["n_cliques"] == 2 and d["n_messages"] == 2
@@ -44,6 +53,7 @@ def test_plan_only_needs_no_gpu_and_device_plans_fail_loudly_without_one():
     if _capi.device_count() == 0:
         with pytest.raises(_capi.JtpError, match="no CPU fallback"):
             engine.Plan([0, (2, [1])], [[1, 2], [2, 3], [2]], {1: 2, 2: 3, 3: 2})
+        assert live_bytes() == (0, 0)                        # (nothing was allocated, nothing is held)
 
 
 def test_package_version_is_the_librarys():

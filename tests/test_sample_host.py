@@ -38,7 +38,7 @@ def test_jtp_sample_is_exported_and_bound():
     assert "jtp_sample" in _capi.SYMBOLS
     fn = _capi.lib().jtp_sample
     assert fn.argtypes is not None and len(fn.argtypes) == 5
-    assert _capi.lib().jtp_version().decode().split()[1] == "0.8.0"
+    assert _capi.lib().jtp_version().decode().split()[1] == "0.8.1"
 
 
 def test_a_plan_only_plan_raises_and_does_not_crash():
