@@ -292,6 +292,25 @@ int jtp_get_log_z(jtp_plan *plan, int32_t batch, double *log_abs_z, int32_t *sig
  * of such (clique, sample) pairs and the first clique. */
 int jtp_sample(jtp_plan *plan, int32_t batch, int32_t n_samples, uint64_t seed, int32_t *states);
 
+/* Expected counts: the weighted sum over evidence sets [batch_begin, batch_end) of the NORMALISED marginals of a request list
+ * (requests as in jtp_get_marginals), formed and accumulated on the device:
+ *     host[out_off[i] + h] = sum_b  weights[b - batch_begin] * m_bi[h] / S_bi ,   S_bi = sum_h m_bi[h]
+ * m_bi = the marginal jtp_get_marginals(plan, b, ...) would return for request i.  weights NULL: all 1; they must be finite
+ * (JTP_EINVAL before any device work), and a set of weight exactly 0 contributes nothing whatever its tables hold.
+ * log_abs_z, z_sign (both NULL, or [batch_end - batch_begin] each): what jtp_get_log_z reports per set, weight 0 included.
+ * Every request is divided by its own sum, so the power of two a JTP_SCALED plan keeps per node cancels.  Works wherever
+ * jtp_get_marginals works on a plan of one rank (JTP_MULTISET, JTP_SHARE_POTENTIALS, n_batch, cover_*, JTP_SCALED);
+ * n_ranks > 1: JTP_EUNSUPPORTED.  The sets are worked in chunks of as many as fit 64 MiB of partial copies (one host wait
+ * per chunk, one copy back per call); S_bi is added in an order that depends on the request's entry count alone and a set is
+ * added to the running sums after every set before it, so the result does not depend on the chunk size bit for bit.
+ * A pair (b, i) with a nonzero weight whose S_bi is zero or not finite (evidence of probability zero, overflow on a plan without
+ * JTP_SCALED) contributes nothing: every output is still written, the call returns JTP_EINVAL and the message names the number of
+ * such pairs and the first (set, request).  Tables with negative entries are accepted as everywhere else, but the sums are
+ * "counts" for non-negative models only. */
+int jtp_accumulate_marginals(jtp_plan *plan, int32_t batch_begin, int32_t batch_end, const double *weights, int32_t n,
+                             const int32_t *cliques, const int32_t *var_off, const int32_t *var_ids, const int64_t *out_off,
+                             double *host, double *log_abs_z, int32_t *z_sign);
+
 /* ---- instrumentation ------------------------------------------------------------------ */
 
 /* Device timing of the next `keep` propagates with hipEvents on the plan's stream (ring; 0
@@ -317,7 +336,7 @@ int jtp_get_launch_ms(jtp_plan *plan, double *ms, int32_t n);
 int jtp_debug_read_msg(jtp_plan *plan, int32_t batch, int64_t off, int64_t n, double *host);
 /* Test hooks.  knob "flow_debug": JtFlow::dbg of the following propagates (8 = every dataflow wait times
  * out after 20 ms: exercises the fall-back to one launch per level); "flow": 0 = launch per level from now on;
- * "fail_alloc": see jtp_debug_live_bytes. */
+ * "fail_alloc": see jtp_debug_live_bytes; "acc_chunk": evidence sets per chunk of jtp_accumulate_marginals (0: by size). */
 int jtp_debug_set(jtp_plan *plan, const char *knob, int64_t value);
 /* Test hook: bytes of device memory and of pinned host memory the library holds right now, process-wide (every plan's buffers;
  * either pointer may be NULL).  With knob "fail_alloc" of jtp_debug_set (the N-th allocation of the plan from now on reports

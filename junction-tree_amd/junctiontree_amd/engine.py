@@ -436,6 +436,71 @@ class Plan:
         _capi.check(rc)
         return out
 
+    def accumulate_marginals(self, requests, weights=None, batch_begin=0, batch_end=None):
+        """Expected counts (`jtp_accumulate_marginals`): for `requests` = [(clique, labels), ...] the sum over the evidence sets
+        [batch_begin, batch_end) of `weights[b - batch_begin]` x the marginal `marginals(requests, batch=b)` would return, each
+        divided by its own sum - formed and added up on the device, one copy back for the whole range.  Returns (list of float64
+        arrays, log|Z_b| per set, sign of Z_b per set).  `weights` None: all 1; a set of weight 0 contributes nothing, its log Z
+        is still reported.
+
+        A (set, request) pair without mass - evidence of probability zero, tables that overflowed on a plan without `scaled` -
+        contributes nothing; `_capi.JtpError` is then raised, with the sums of the other pairs as its `counts` attribute and the
+        logarithms as `log_z` (`z_sign`: the signs)."""
+        end = self.n_batch if batch_end is None else int(batch_end)
+        begin = int(batch_begin)
+        w = self._weights(weights, begin, end)
+        n = len(requests)
+        cliques = _int_array([self.abi_of[c] for c, _ in requests] + [0])
+        var_off, var_ids, out_off, shapes = [0], [], [0], []
+        for _, labels in requests:
+            var_ids += [self.var_id[lab] for lab in labels if lab not in self._trivial]
+            var_off.append(len(var_ids))
+            shape = tuple(1 if lab in self._trivial else self.card[self.var_id[lab]] for lab in labels)
+            shapes.append(shape)
+            out_off.append(out_off[-1] + (int(np.prod(shape, dtype=np.int64)) if shape else 1))
+        keep = (cliques, _int_array(var_off), _int_array(var_ids + [0]), (C.c_int64 * (n + 1))(*out_off))
+        return self._accumulate(n, [C.addressof(k) for k in keep], out_off, shapes, w, begin, end)
+
+    def factor_counts(self, factor_labels, factor_to_clique, weights=None, batch_begin=0, batch_end=None):
+        """`accumulate_marginals` with the request list `factor_marginals` reads: one request per factor, on its clique."""
+        end = self.n_batch if batch_end is None else int(batch_end)
+        w = self._weights(weights, int(batch_begin), end)
+        req = self.__dict__.get("_marginal_requests")
+        if req is None or not (req.f2c == list(factor_to_clique) and _same_lists(req.labels, factor_labels)):
+            req = self._marginal_requests = _MarginalRequests(self, (tuple(map(tuple, factor_labels)), tuple(factor_to_clique)))
+        req.src = (factor_labels, factor_to_clique)
+        args = [req.cliques.ctypes.data, req.var_off.ctypes.data, req.var_ids.ctypes.data, req.out_off.ctypes.data]
+        return self._accumulate(req.n, args, req.bounds, req.shapes, w, int(batch_begin), end)
+
+    @staticmethod
+    def _weights(weights, begin, end):
+        if weights is None:
+            return None
+        w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+        if len(w) != max(end - begin, 0):
+            raise ValueError("%d weights for %d evidence sets" % (len(w), max(end - begin, 0)))
+        if not np.isfinite(w).all():
+            raise ValueError("weights must be finite")
+        return w
+
+    def _accumulate(self, n, args, out_off, shapes, w, begin, end):
+        n_sets = max(end - begin, 0)
+        flat = np.zeros(max(out_off[-1], 1), dtype=np.float64)
+        log_z = np.zeros(max(n_sets, 1), dtype=np.float64)
+        sign = np.zeros(max(n_sets, 1), dtype=np.int32)
+        rc = self._lib.jtp_accumulate_marginals(self._handle, begin, end, None if w is None else w.ctypes.data, n, *args,
+                                                flat.ctypes.data, log_z.ctypes.data, sign.ctypes.data)
+        out = [flat[out_off[i]:out_off[i + 1]].reshape(shapes[i]).copy() for i in range(n)]
+        log_z, sign = log_z[:n_sets], sign[:n_sets]
+        if rc == _capi.JTP_EINVAL:
+            msg = self._lib.jtp_last_error().decode("utf-8", "replace")
+            if "without mass" in msg:
+                err = _capi.JtpError(msg)
+                err.counts, err.log_z, err.z_sign = out, log_z, sign
+                raise err
+        _capi.check(rc)
+        return out, log_z, sign
+
     # ------------------------------------------------------------------ instrumentation
     def set_profiling(self, keep=1, per_launch=False, stride=1):
         """Time the next `keep` propagates with hipEvents on the plan's stream: three events per

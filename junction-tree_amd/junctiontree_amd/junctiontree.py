@@ -330,11 +330,22 @@ class JunctionTree:
         `normalize`: the sets run on an overflow-safe plan (`engine.Plan(scaled=True, share_potentials=True)`: one pass per set
         over the shared tables - scaled multi-set plans are not built), every marginal is divided by its own sum, and
         `tree.log_z_sets[e]` is log|Z_e|: log P(evidence e) = log_z_sets[e] - that of a set observing nothing."""
-        from . import engine
-
         ct = self.clique_tree
         if not evidence_sets:
             return []
+        plan = self._propagated_evidence_plan(xs, evidence_sets, normalize)
+        if normalize:
+            out = [_normalised(plan.factor_marginals(ct.factor_graph.factors, ct.factor_to_maxclique, batch=b)) for b in range(len(evidence_sets))]
+            self._memo["log_z_sets"] = np.array([plan.log_z(batch=b)[1] for b in range(len(evidence_sets))])
+            return out
+        return [plan.factor_marginals(ct.factor_graph.factors, ct.factor_to_maxclique, batch=b) for b in range(len(evidence_sets))]
+
+    def _propagated_evidence_plan(self, xs, evidence_sets, normalize):
+        """The plan `propagate_evidence_sets` and `expected_counts` run a non-empty list of evidence sets on, with the factor values
+        staged, the evidence set and every set propagated (enqueued, not waited for)."""
+        from . import engine
+
+        ct = self.clique_tree
         all_f32 = all(isinstance(x, np.ndarray) and x.dtype == np.float32 for x in xs)
         node_vars = [list(c) for c in ct.maxcliques] + [list(s) for s in self.separators]
         # one copy of the tables; eight evidence sets per pass over a table (JTP_MULTISET), marginals formed
@@ -344,33 +355,58 @@ class JunctionTree:
             plan = engine.plan_for(self.tree, node_vars, ct.factor_graph.sizes, "f32" if all_f32 else "f64",
                                    n_batch=len(evidence_sets), share_potentials=True, scaled=True, cover=self.cover(), **self._opts)
             plan.evidence_mode = "one pass per evidence set over shared tables (scaled plan: messages divided by powers of two)"
-            self._memo["evidence_plan"] = plan
-            _stage_changed_cliques(plan, ct, xs)
-            for b, observed in enumerate(evidence_sets):
-                plan.set_evidence(observed, batch=b)
-            plan.propagate(0, len(evidence_sets))
-            out = [_normalised(plan.factor_marginals(ct.factor_graph.factors, ct.factor_to_maxclique, batch=b)) for b in range(len(evidence_sets))]
-            self._memo["log_z_sets"] = np.array([plan.log_z(batch=b)[1] for b in range(len(evidence_sets))])
-            return out
-        try:
-            plan = engine.plan_for(self.tree, node_vars, ct.factor_graph.sizes, "f32" if all_f32 else "f64",
-                                   n_batch=len(evidence_sets), multiset=True, **self._opts)
-            plan.evidence_mode = "multiset: eight evidence sets per pass over a table"
-        except UnsupportedStructure as exc:
-            # separators too large for the per-set LDS regions of a multi-set pass (e.g. 64 x 64 doubles): the sets
-            # still share one copy of the tables but run one pass each, one HIP stream each - up to eight times the table traffic
-            # of a multi-set plan, so it is said, not done silently (`plan.evidence_mode`, and a warning once per tree)
-            import warnings
-            plan = engine.plan_for(self.tree, node_vars, ct.factor_graph.sizes, "f32" if all_f32 else "f64",
-                                   n_batch=len(evidence_sets), share_potentials=True, cover=self.cover(), **self._opts)
-            plan.evidence_mode = "one pass per evidence set over shared tables (the multi-set plan was refused: %s)" % exc
-            if not self._memo.get("warned_multiset"):
-                self._memo["warned_multiset"] = True
-                warnings.warn("junctiontree_amd: the evidence sets of this tree run one pass each instead of eight per pass (%s)" % exc,
-                              RuntimeWarning, stacklevel=2)
+        else:
+            try:
+                plan = engine.plan_for(self.tree, node_vars, ct.factor_graph.sizes, "f32" if all_f32 else "f64",
+                                       n_batch=len(evidence_sets), multiset=True, **self._opts)
+                plan.evidence_mode = "multiset: eight evidence sets per pass over a table"
+            except UnsupportedStructure as exc:
+                # separators too large for the per-set LDS regions of a multi-set pass (e.g. 64 x 64 doubles): the sets
+                # still share one copy of the tables but run one pass each, one HIP stream each - up to eight times the table traffic
+                # of a multi-set plan, so it is said, not done silently (`plan.evidence_mode`, and a warning once per tree)
+                import warnings
+                plan = engine.plan_for(self.tree, node_vars, ct.factor_graph.sizes, "f32" if all_f32 else "f64",
+                                       n_batch=len(evidence_sets), share_potentials=True, cover=self.cover(), **self._opts)
+                plan.evidence_mode = "one pass per evidence set over shared tables (the multi-set plan was refused: %s)" % exc
+                if not self._memo.get("warned_multiset"):
+                    self._memo["warned_multiset"] = True
+                    warnings.warn("junctiontree_amd: the evidence sets of this tree run one pass each instead of eight per pass (%s)" % exc,
+                                  RuntimeWarning, stacklevel=3)
         self._memo["evidence_plan"] = plan
         _stage_changed_cliques(plan, ct, xs)
         for b, observed in enumerate(evidence_sets):
             plan.set_evidence(observed, batch=b)
         plan.propagate(0, len(evidence_sets))
-        return [plan.factor_marginals(ct.factor_graph.factors, ct.factor_to_maxclique, batch=b) for b in range(len(evidence_sets))]
+        return plan
+
+    def expected_counts(self, values, evidence_sets, weights=None, normalize=False):
+        """The E-step of EM (not in the reference): one float64 array per factor, of the factor's shape, holding
+        sum_e weights[e] * P(the factor's variables | evidence set e) - every set's factor marginal divided by its own sum, added up
+        on the device (`engine.Plan.accumulate_marginals`: nothing but the sums crosses to the host).  `evidence_sets` as in
+        `propagate_evidence_sets` (one {variable: observed state} per data case), `weights` None: all 1.
+
+        `tree.log_z_sets[e]` is then log|Z_e|, whatever the weight: add `{}` as one more set with weight 0 to obtain log Z of the
+        model without evidence, and hence log P(evidence e) = log_z_sets[e] - log_z_sets[-1], the terms of the data log-likelihood.
+        The plan is chosen as `propagate_evidence_sets` chooses it (`normalize`: the overflow-safe plan).  A set whose evidence has
+        probability zero contributes nothing; `_capi.JtpError` is raised, carrying the sums of the other sets as `counts` and the
+        logarithms as `log_z`.  The sums are counts for non-negative factor values only."""
+        ct = self.clique_tree
+        n_sets = len(evidence_sets)
+        if weights is not None:
+            weights = np.asarray(weights, dtype=np.float64).reshape(-1)
+            if len(weights) != n_sets:
+                raise ValueError("%d weights for %d evidence sets" % (len(weights), n_sets))
+            if not np.isfinite(weights).all():
+                raise ValueError("weights must be finite")
+        if n_sets == 0:
+            self._memo["log_z_sets"] = np.zeros(0)
+            return [np.zeros(np.shape(x), dtype=np.float64) for x in values]
+        plan = self._propagated_evidence_plan(values, evidence_sets, normalize)
+        try:
+            out, log_z, _ = plan.factor_counts(ct.factor_graph.factors, ct.factor_to_maxclique, weights=weights, batch_begin=0, batch_end=n_sets)
+        except Exception as exc:
+            if hasattr(exc, "log_z"):
+                self._memo["log_z_sets"] = np.array(exc.log_z)
+            raise
+        self._memo["log_z_sets"] = np.array(log_z)
+        return out
