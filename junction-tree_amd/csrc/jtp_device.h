@@ -1,4 +1,4 @@
-// Owning buffers for the engine's device and pinned host memory (jtp_engine.hip only).
+// Owning buffers for the engine's device and pinned host memory (the engine's translation units only: jtp_engine.h).
 // A buffer is either empty or holds one complete allocation: every operation that fails leaves it empty, so `if (!buf)` is
 // a correct "not built yet" test.  Each buffer books its bytes with its plan's MemLedger (jtp_stats.device_bytes) and with the
 // process-wide counters behind jtp_debug_live_bytes; the ledger also carries the test hook that makes an allocation fail.
@@ -16,7 +16,7 @@ struct MemLedger {
                                 // hipErrorOutOfMemory on the host, without calling HIP; 0: off
 };
 
-static std::atomic<int64_t> g_live_bytes[2];       // [0] device, [1] pinned host: the whole process
+inline std::atomic<int64_t> g_live_bytes[2];       // [0] device, [1] pinned host: the whole process (ONE object for all units)
 
 template <typename T, bool PINNED>
 class MemBuf {

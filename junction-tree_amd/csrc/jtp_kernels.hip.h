@@ -1846,7 +1846,7 @@ __global__ __launch_bounds__(JT_THREADS, 3) void jt_distribute_level(const JtTas
 // waits cannot deadlock as long as no workgroup is dispatched before one with a lower index (then the
 // lowest unfinished workgroup is always running, and it never waits on an unfinished one).  That is
 // how the hardware dispatches; should it ever not be, the wait times out, the host notices and runs
-// the propagate again with one launch per level (jtp_engine.hip: check_flow).  With JTP_FLOW_TICKETS
+// the propagate again with one launch per level (jtp_propagate.hip: check_flow).  With JTP_FLOW_TICKETS
 // the list position is drawn from an atomic counter instead, which needs no such assumption but costs
 // a memory round trip before anything else can start (~10% on the benchmark tree).
 __device__ __forceinline__ uint32_t jt_flow_ticket(const JtFlow &fl, uint32_t *flow_ctl) {
@@ -2502,36 +2502,11 @@ __device__ __forceinline__ void jt_mpass(const JtTask &tk, const JtBlock &bk, co
 #endif
 }
 
-// Evidence-free subtrees (rounds 5-6).  Arena slot 0 of a multi-set plan holds a set that observes nothing.  The upward message of a
-// clique below which a set observes nothing IS slot 0's: the set is not on that collect task's active list (JtFlow::act_ids), consumers
-// and the read-out take the message from slot 0 (JtFlow::skip / jtp_engine.hip readout_redirect), and the set's own entries of it stay
-// "unwritten" in both arena halves - which this pass restores, once, for the (task, set) pairs that LEAVE a list when the evidence changes.
-#define JT_FANOUT_RESET 0x20000000
-struct JtFanout {
-    int64_t off;               // msg-arena offset (doubles) of the entries
-    int32_t count;             // doubles
-    int32_t flags;             // JT_FANOUT_RESET: the entries of BOTH arena halves of the listed slots become "unwritten"
-    uint16_t slot[JT_MSETS];   // the arena slots concerned (0xffff: none)
-};
-#ifndef JT_INST_TU
-// (fl.oth_off: the distance of the second arena half from the first)
-__global__ __launch_bounds__(256) void jt_multi_fanout(const JtFanout *__restrict__ list, double *__restrict__ msg, JtFlow fl) {
-    const JtFanout f = list[blockIdx.x];
-    if (!(f.flags & JT_FANOUT_RESET)) return;
-    for (int i = threadIdx.x; i < f.count; i += 256)
-#pragma unroll
-        for (int s = 0; s < JT_MSETS; ++s) {
-            if (f.slot[s] == 0xffffu) continue;
-            double *base = msg + (int64_t)f.slot[s] * fl.set_stride + f.off + i;
-            base[0] = __longlong_as_double((long long)JT_UNWRITTEN);
-            base[fl.oth_off] = __longlong_as_double((long long)JT_UNWRITTEN);
-        }
-}
-#endif
-
-// Multi-set entry point: grid.y = group of JT_MSETS evidence sets; the block list is that of a whole phase
-// (dataflow launch) or of one tree level.  Workgroups of one group only ever wait for workgroups of the same
-// group earlier in the list.
+// Multi-set entry point: the GROUP of JT_MSETS evidence sets is folded into the 1-D block index; the block list is that of a
+// whole phase (dataflow launch) or of one tree level.  A workgroup waits for workgroups earlier in the list - of its own group,
+// and, where sets share the messages of evidence-free subtrees (JtFlow::act_ids / JtFlow::skip), of the group that holds arena
+// slot 0 or the slot on the producer's active list.  The ticket counters are per group, so these waits across groups rest on
+// in-order dispatch and on the host's abort (JtFlow::host_abort).
 #ifndef JT_MULTI_WAVES
 #define JT_MULTI_WAVES 3
 #endif
@@ -2778,294 +2753,6 @@ __global__ __launch_bounds__(JT_THREADS) void jt_distribute(const JtTask *__rest
     const JtBlock &bk = blk[blockIdx.x];
     jt_pass<T, HASP + NCH, NCH, 1>(tasks[bk.task], bk, itab, psi, bel, msg, fl, blockIdx.x);
 }
-
-// ------------------------------------------------------------------------------------------
-// Layout conversion and synthetic fill (off the hot path).
-
-__device__ __forceinline__ uint64_t jt_splitmix64(uint64_t x) {
-    uint64_t z = x + 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
-// digit of variable i at device (physical) element index x: a shift where the variable is a bit field
-__device__ __forceinline__ int jt_digit(const JtPackDesc &d, int i, uint32_t x) {
-    const uint32_t ds = d.dstride[i];
-    if (d.row_elems > 0 && i == d.split_var)               // the variable across the thread part's top bit: low digit of the row, high digit above
-        return (int)(((x % (uint32_t)d.row_elems) / ds) % (uint32_t)d.dmod[i]) + ((int)((x / d.split_ds2) % (uint32_t)d.split_mod2) << d.split_lb);
-    if (d.row_elems > 0 && d.pos[i] < d.low_bits)          // a mixed-radix digit of the row (thread part at true cardinalities)
-        return ds > 0 ? (int)(((x % (uint32_t)d.row_elems) / ds) % (uint32_t)d.dmod[i]) : 0;
-    if (ds == (1u << d.pos[i]) && d.dmod[i] == (1 << d.nb[i])) return (int)((x >> d.pos[i]) & ((1u << d.nb[i]) - 1u));
-    return ds > 0 ? (int)((x / ds) % (uint32_t)d.dmod[i]) : 0;
-}
-
-// device index -> host index; returns false for entries that name no table entry (padding inside the thread part)
-__device__ __forceinline__ bool jt_dev_to_host(const JtPackDesc &d, uint32_t x, int64_t &hidx) {
-    bool valid = true;
-    int64_t h = 0, back = 0;
-    for (int i = 0; i < d.nvars; ++i) {
-        const int digit = jt_digit(d, i, x);
-        valid = valid && (digit < d.card[i]);
-        h += (int64_t)digit * d.hstride[i];
-        if (d.row_elems > 0 && i == d.split_var)
-            back += (int64_t)(digit & ((1 << d.split_lb) - 1)) * d.dstride[i] + (int64_t)(digit >> d.split_lb) * d.split_ds2;
-        else
-        back += (int64_t)digit * d.dstride[i];
-    }
-    if (back != (int64_t)x) valid = false;              // index bits no variable owns must be clear
-    hidx = h;
-    return valid;
-}
-
-// MODE 0: arena[x] = stage[host index] (pack);  MODE 1: synthetic fill
-// MODE 2: 1 where the index names an entry, else 0 (tables of virtual cliques)
-template <typename T, typename S, int MODE>
-__global__ __launch_bounds__(256) void jt_pack(JtPackDesc d, const S *__restrict__ stage, T *__restrict__ arena,
-                                               uint64_t key, double scale) {
-    const int64_t n = d.phys_elems;
-    for (int64_t x = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; x < n; x += (int64_t)gridDim.x * blockDim.x) {
-        int64_t h;
-        const bool valid = jt_dev_to_host(d, (uint32_t)x, h);
-        double v = 0.0;
-        if (valid) {
-            if constexpr (MODE == 0) v = (double)stage[h];
-            else if constexpr (MODE == 2) v = 1.0;
-            else {
-                const uint64_t bits = jt_splitmix64(key + (uint64_t)h);
-                v = (0.5 + (double)(bits >> 11) * (1.0 / 9007199254740992.0)) * scale;
-            }
-        }
-        arena[d.dev_off + x] = (T)v;
-    }
-}
-
-#ifndef JT_INST_TU      // (the kernels that are not templates are defined in ONE translation unit: the engine's)
-// JTP_FAKE_COMM: stand-in for a received message
-__global__ __launch_bounds__(256) void jt_fill_value(double *__restrict__ dst, int64_t n, double v) {
-    for (int64_t x = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; x < n; x += (int64_t)gridDim.x * blockDim.x) dst[x] = v;
-}
-#endif
-
-// Clique potentials = products of factor tables, written in the cliques' device layouts: CliqueGraph.evaluate
-// (junctiontree/junctiontree.py:203-226) for a LIST of cliques in ONE launch (jtp_set_potential_products).
-// Bound: HBM writes (sizeof(T) per element; the factor tables are small and sit in LDS, or are gathered through L2).
-// A workgroup forms JT_EVAL_ROWS consecutive stored rows of one clique.  The element at x = row * row_len + t has
-// digit_i(x) = digit_i(t) + digit_i(row * row_len) for every variable i (jt_digit is additive over the two parts: a variable
-// lies inside the row, above it, or - one variable at most, JtEvalTask::straddle - has a low part inside and a high part
-// above), so every factor's table index is tin[f](t) + rin[f](row): the divisions happen once per thread and once per
-// row.  (Round 3's jt_eval_product decoded every element: 9.2 GiB of config-3 tables in 31 ms, 0.3 TB/s.)
-template <typename T>
-__global__ __launch_bounds__(256) void jt_eval_batch(const JtEvalTask *__restrict__ tasks, const int32_t *__restrict__ blk_start, int ntasks,
-                                                     const JtEvalVar *__restrict__ fvars, const char *__restrict__ stage, T *__restrict__ arena) {
-    constexpr int VEC = 16 / sizeof(T);
-    typedef T ext_t __attribute__((ext_vector_type(VEC)));
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    double *lds_tab = reinterpret_cast<double *>(smem);
-    __shared__ int32_t s_rin[JT_EVAL_ROWS][JT_EVAL_MAX_F];
-    __shared__ int32_t s_rdig[JT_EVAL_ROWS], s_rok[JT_EVAL_ROWS];
-    // (the records are read from memory, not passed as kernel arguments: hipcc (ROCm 7.2) mis-read the 32-bit arrays of a
-    //  kernel-argument struct when indexed with a run-time index - dstride[cvar] came back as dstride[0])
-    int lo = 0, hi = ntasks;
-    const int b = (int)blockIdx.x;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (blk_start[mid] <= b) lo = mid;
-        else hi = mid;
-    }
-    const JtEvalTask &tk = tasks[lo];
-    const JtPackDesc &c = tk.clique;
-    const int tid = (int)threadIdx.x;
-    const int row0 = (b - blk_start[lo]) * JT_EVAL_ROWS;
-    const int nrows = tk.n_rows - row0 < JT_EVAL_ROWS ? tk.n_rows - row0 : JT_EVAL_ROWS;
-    const int L = tk.row_len, nf = tk.nf, sv = tk.straddle;
-    const int scard = sv >= 0 ? c.card[sv] : 1;
-    // small factor tables -> LDS, as doubles
-#pragma unroll
-    for (int f = 0; f < JT_EVAL_MAX_F; ++f) {
-        if (f >= nf || tk.flds[f] < 0) continue;
-        double *dst = lds_tab + tk.flds[f];
-        const int n = tk.felems[f];
-        if (tk.fis64[f]) {
-            const double *src = reinterpret_cast<const double *>(stage) + tk.foff[f];
-            for (int i = tid; i < n; i += 256) dst[i] = src[i];
-        } else {
-            const float *src = reinterpret_cast<const float *>(stage) + tk.foff[f];
-            for (int i = tid; i < n; i += 256) dst[i] = (double)src[i];
-        }
-    }
-    // place x (x = t inside the first row, or x = row * row_len) -> is it the part of a table entry, the straddling
-    // variable's part of its digit, and every factor's part of its table index
-    auto decode = [&](const uint32_t x, const bool high, int &sdig, int (&fidx)[JT_EVAL_MAX_F]) {
-        bool ok = true;
-        int64_t back = 0;
-        sdig = 0;
-        for (int i = 0; i < c.nvars; ++i) {
-            const int d = jt_digit(c, i, x);
-            if (i == sv) sdig = d;
-            else ok = ok && d < c.card[i];
-            if (c.row_elems > 0 && i == c.split_var)
-                back += high ? (int64_t)(d >> c.split_lb) * c.split_ds2 : (int64_t)d * c.dstride[i];
-            else
-                back += (int64_t)d * c.dstride[i];
-        }
-        ok = ok && back == (int64_t)x;          // index bits no variable owns must be clear
-#pragma unroll
-        for (int f = 0; f < JT_EVAL_MAX_F; ++f) {
-            int idx = 0;
-            if (f < nf && ok) {
-                const JtEvalVar *fv = fvars + tk.fv_off[f];
-                for (int j = 0; j < tk.fnv[f]; ++j) {
-                    const uint32_t ds = fv[j].ds;
-                    const uint32_t xr = fv[j].kind ? x % (uint32_t)c.row_elems : x;
-                    int digit = ds > 0 ? (int)((xr / ds) % (uint32_t)fv[j].mod) : 0;
-                    if (fv[j].kind == 2) digit += (int)((x / c.split_ds2) % (uint32_t)c.split_mod2) << c.split_lb;
-                    idx += digit * fv[j].stride;
-                }
-            }
-            fidx[f] = idx;
-        }
-        return ok;
-    };
-    int tin[VEC][JT_EVAL_MAX_F], tdig[VEC];
-    bool tok[VEC];
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) {
-        const int t = tid * VEC + e;
-        tok[e] = decode((uint32_t)(t < L ? t : 0), false, tdig[e], tin[e]) && t < L;
-    }
-    if (tid < nrows) {
-        int hd, rin[JT_EVAL_MAX_F];
-        const bool ok = decode((uint32_t)(row0 + tid) * (uint32_t)L, true, hd, rin);
-        s_rok[tid] = ok ? 1 : 0;
-        s_rdig[tid] = hd;
-#pragma unroll
-        for (int f = 0; f < JT_EVAL_MAX_F; ++f) s_rin[tid][f] = rin[f];
-    }
-    __syncthreads();
-    const bool active = tid * VEC < L;
-    T *row = arena + c.dev_off + (int64_t)row0 * L + tid * VEC;
-    for (int r = 0; r < nrows; ++r, row += L) {
-        const bool rok = s_rok[r] != 0;
-        const int hd = s_rdig[r];
-        bool ok[VEC];
-        double v[VEC];
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) {
-            ok[e] = tok[e] && rok && tdig[e] + hd < scard;
-            v[e] = 1.0;
-        }
-        if (tk.accumulate && active) {
-            const ext_t old = *reinterpret_cast<const ext_t *>(row);
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) v[e] = (double)old[e];
-        }
-#pragma unroll
-        for (int f = 0; f < JT_EVAL_MAX_F; ++f) {
-            if (f >= nf) continue;
-            const int ri = s_rin[r][f];
-            if (tk.flds[f] >= 0) {
-                const double *tab = lds_tab + tk.flds[f];
-#pragma unroll
-                for (int e = 0; e < VEC; ++e) v[e] *= tab[ok[e] ? tin[e][f] + ri : 0];
-            } else if (tk.fis64[f]) {
-                const double *tab = reinterpret_cast<const double *>(stage) + tk.foff[f];
-#pragma unroll
-                for (int e = 0; e < VEC; ++e) v[e] *= tab[ok[e] ? tin[e][f] + ri : 0];
-            } else {
-                const float *tab = reinterpret_cast<const float *>(stage) + tk.foff[f];
-#pragma unroll
-                for (int e = 0; e < VEC; ++e) v[e] *= (double)tab[ok[e] ? tin[e][f] + ri : 0];
-            }
-        }
-        if (active) {
-            ext_t ov;
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) ov[e] = ok[e] ? (T)v[e] : (T)0;
-            __builtin_nontemporal_store(ov, reinterpret_cast<ext_t *>(row));
-        }
-    }
-}
-
-// host index -> device index
-__device__ __forceinline__ uint32_t jt_host_to_dev(const JtPackDesc &d, int64_t h) {
-    uint32_t x = 0;
-    for (int i = d.nvars - 1; i >= 0; --i) {
-        const int c = d.card[i];
-        const int digit = (int)(h % c);
-        h /= c;
-        if (d.row_elems > 0 && i == d.split_var)
-            x += (uint32_t)(digit & ((1 << d.split_lb) - 1)) * d.dstride[i] + (uint32_t)(digit >> d.split_lb) * d.split_ds2;
-        else
-        x += (uint32_t)digit * d.dstride[i];
-    }
-    return x;
-}
-
-template <typename T, typename S>
-__global__ __launch_bounds__(256) void jt_unpack(JtPackDesc d, const T *__restrict__ arena, S *__restrict__ stage) {
-    for (int64_t h = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; h < d.host_elems;
-         h += (int64_t)gridDim.x * blockDim.x)
-        stage[h] = (S)arena[d.dev_off + jt_host_to_dev(d, h)];
-}
-
-// message(s) -> host order: out[h] = (sum_p up[p]) * (dn ? sum_p dn[p] : 1)
-template <typename S>
-__global__ __launch_bounds__(256) void jt_msg_unpack(JtPackDesc d, const double *__restrict__ up, int up_npart,
-                                                     const double *__restrict__ dn, int dn_npart, int64_t pstride,
-                                                     S *__restrict__ stage) {
-    for (int64_t h = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; h < d.host_elems;
-         h += (int64_t)gridDim.x * blockDim.x) {
-        const uint32_t x = jt_host_to_dev(d, h);
-        double u = 0.0;
-        for (int p = 0; p < up_npart; ++p) u += up[(int64_t)p * pstride + x];
-        if (dn) {
-            double w = 0.0;
-            for (int p = 0; p < dn_npart; ++p) w += dn[(int64_t)p * pstride + x];
-            u *= w;
-        }
-        stage[h] = (S)u;
-    }
-}
-
-#ifndef JT_INST_TU
-// batched marginal read-out: request blockIdx.y, entries strided over blockIdx.x
-// (round 6: a factor marginal is a few dozen entries of hundreds of partial copies - one per workgroup of the pass that formed it; a
-//  thread per entry added them one after the other, 94 us for config 3's 1831 requests.  A request of at most 128 entries now spreads
-//  its copies over 256 / entries thread groups - group g takes copies g, g + G, ... - whose sums are added in group order: a fixed
-//  order, the same bits on every call.)
-__global__ __launch_bounds__(256) void jt_marg_unpack(const JtMargDesc *__restrict__ descs, const double *__restrict__ scratch_buf,
-                                                      double *__restrict__ stage, const double *__restrict__ arena_cur) {
-    const JtMargDesc &m = descs[blockIdx.y];
-    const double *scratch = m.in_arena ? arena_cur : scratch_buf;       // (a marginal a folded task left in the message arena)
-    __shared__ double part[256];
-    const int64_t ne = m.d.host_elems;
-    if (ne <= 128 && gridDim.x == 1) {
-        int w = 1;
-        while (w < ne) w <<= 1;                                   // entries rounded up to a power of two
-        const int G = 256 / w, g = (int)threadIdx.x / w, h = (int)threadIdx.x % w;
-        double u = 0.0;
-        if (h < ne) {
-            const uint32_t x = jt_host_to_dev(m.d, h);
-            for (int p = g; p < m.npart; p += G) u += scratch[m.src_off + (int64_t)p * m.pstride + x];
-        }
-        part[threadIdx.x] = u;
-        __syncthreads();
-        if (g == 0 && h < ne) {
-            double t = part[h];
-            for (int k = 1; k < G; ++k) t += part[k * w + h];
-            stage[m.dst_off + h] = t;
-        }
-        return;
-    }
-    for (int64_t h = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; h < ne; h += (int64_t)gridDim.x * blockDim.x) {
-        const uint32_t x = jt_host_to_dev(m.d, h);
-        double u = 0.0;
-        for (int p = 0; p < m.npart; ++p) u += scratch[m.src_off + (int64_t)p * m.pstride + x];
-        stage[m.dst_off + h] = u;
-    }
-}
-#endif
 
 // ------------------------------------------------------------------------------------------
 // Explicit instantiation lists.  The message-passing kernels are compiled in translation units of their own, in parallel

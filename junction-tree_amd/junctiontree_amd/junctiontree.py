@@ -265,7 +265,8 @@ class JunctionTree:
         # cliques whose factors changed since this plan last saw them (the reference recomputes every clique on
         # every call and says so in a FIXME, junctiontree.py:206-214)
         _stage_changed_cliques(plan, ct, xs, changed=changed)
-        # (no wait here: the marginal kernels are enqueued behind the propagate while it runs, and `jtp_get_marginals` waits once for all)
+        # (no wait here: `jtp_get_marginals` waits.  After a dataflow propagate it first waits for the stream and looks at the abort flag
+        #  (settle), then enqueues the marginal kernels; only behind per-level launches are they enqueued while the propagate runs)
         plan.propagate(sync=False)
         # marginalize (junctiontree.py:229-274) on the device: one launch for all factors, the factors of one clique
         # sharing the passes over its belief table

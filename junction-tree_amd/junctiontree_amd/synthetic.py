@@ -3,7 +3,7 @@
 Host-side helpers shared by `bench.py`, the tests and the golden-vector generator.  The
 value generator is counter based (splitmix64 of a per-node key plus the element's linear
 index in the node's *host* C-order layout), so the device can regenerate exactly the same
-numbers in `jtp_fill_synthetic` (csrc/jtp_kernels.hip: `synth_value`) without shipping
+numbers in `jtp_fill_synthetic` (csrc/jtp_upload.hip: `jt_pack`, MODE 1) without shipping
 GiB-sized fixtures, and numpy can regenerate them for the oracle.
 
 Tree recipes follow BASELINE.json's configs:

@@ -1,6 +1,6 @@
 """CPU emulation of JTP_SCALED plans, for tests only: tests/emulator.py with the kind-2 steps of the step list (`rescale` records:
 every copy of one message as its consumers read it, divided by one power of two) executed with numpy by the rule of the kernel
-`jt_rescale_level` (csrc/jtp_engine.hip), clamps included, and the node exponents walked down the planner's tree the way the
+`jt_rescale_level` (csrc/jtp_propagate.hip), clamps included, and the node exponents walked down the planner's tree the way the
 engine's read-out does."""
 import numpy as np
 

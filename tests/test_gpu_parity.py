@@ -721,6 +721,44 @@ def test_event_timing_of_every_nth_propagate():
     plan.close()
 
 
+def test_event_timing_of_a_multi_set_plan_leaves_the_results_alone():
+    """The three phase events of a profiled propagate on a multi-set plan (the event ring is shared with the per-set propagate):
+    a root with two children over a dozen binary and ternary variables, three evidence sets; three propagates with events and
+    three without give the same bits - which are the oracle's beliefs - and the profiled ones report a positive device time."""
+    spec = synthetic.wide_binary_tree(n_cliques=3, width=6, sep=3, card=2, seed=1)
+    sizes = {v: 3 if v % 3 == 0 else 2 for v in spec["sizes"]}
+    n, nb = spec["n_cliques"], 3
+    rng = np.random.default_rng(5)
+    base = [rng.uniform(0.5, 1.5, [sizes[v] for v in labs]) for labs in spec["node_vars"][:n]]
+    base += [np.ones([sizes[v] for v in labs]) for labs in spec["node_vars"][n:]]          # separators (unused values)
+    plan = engine.Plan(spec["tree"], spec["node_vars"], sizes, dtype="f64", n_batch=nb, multiset=True)
+    assert plan.describe()["multiset"] == 1
+    for c in range(n):
+        plan.set_potential(c, base[c])
+    labels = sorted(sizes)
+    observed = [{}, {labels[0]: 1}, {labels[0]: 2, labels[-1]: 1}]
+    for b in range(nb):
+        plan.set_evidence(observed[b], batch=b)
+    got = {}
+    for keep in (2, 0):
+        plan.set_profiling(keep)
+        for _ in range(3):
+            plan.propagate(sync=False)
+        plan.sync()
+        if keep:
+            assert sum(k["ms"] for k in plan.stats()["kernels"].values()) > 0
+        got[keep] = [plan.belief(node, batch=b).copy() for b in range(nb) for node in range(len(spec["node_vars"]))]
+    assert plan.stats()["flow_fallbacks"] == 0
+    for a, b in zip(got[2], got[0]):
+        np.testing.assert_array_equal(a, b)
+    spec3 = dict(spec, sizes=sizes)
+    for b in range(nb):
+        want = oracle.beliefs_exact(spec["tree"], _indicator_potentials(spec3, base, observed[b]), spec["node_vars"])
+        for node in range(len(spec["node_vars"])):
+            close(got[0][b * len(spec["node_vars"]) + node], want[node], what="set %d node %d" % (b, node))
+    plan.close()
+
+
 def test_pinned_host_arrays_in_and_out():
     """Potentials handed over from page-locked arrays (jtp_host_alloc) and beliefs read into them."""
     spec = synthetic.wide_binary_tree(n_cliques=7, width=12, sep=6, card=2, seed=3)
@@ -801,7 +839,7 @@ def test_launch_modes_are_bit_identical():
 
 
 def test_ticket_order_only_while_another_plan_is_in_flight():
-    """Dataflow launches in blockIdx order are unsafe only while ANOTHER dataflow kernel may be resident (jtp_engine.hip:
+    """Dataflow launches in blockIdx order are unsafe only while ANOTHER dataflow kernel may be resident (jtp_propagate.hip:
     enter_flight).  An idle second plan costs nothing; one with an unsynchronised propagate makes the newcomer draw
     tickets; once it has been waited for, blockIdx order is back.  Results are identical either way."""
     spec = synthetic.wide_binary_tree(n_cliques=15, width=14, sep=7, card=2, seed=4)

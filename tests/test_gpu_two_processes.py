@@ -1,5 +1,5 @@
 """Two PROCESSES on one GPU, both with dataflow propagates in flight, no JTP_FLOW_TICKETS in the environment: each finds the
-other through the shared-memory board (/dev/shm/jtprop_flight_<PCI bus id>, jtp_engine.hip `board`) and launches in ticket
+other through the shared-memory board (/dev/shm/jtprop_flight_<PCI bus id>, jtp_propagate.hip `board`) and launches in ticket
 order - no dataflow wait times out, no fall-back to level launches (round 3: an environment variable, else a 2 s stall),
 and the results are the oracle's."""
 import json
