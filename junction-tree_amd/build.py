@@ -17,9 +17,12 @@ LIB = os.path.join(LIBDIR, "libjtprop.so")
 INST = ["jtp_inst_%s_%s.hip" % (fam, t) for fam in ("both", "bothm", "level", "mixc", "mix", "flow", "multi", "shape") for t in ("f32", "f64")]
 # (the engine's units, by concern: csrc/jtp_engine.h has the map)
 ENGINE = ["jtp_engine.hip", "jtp_upload.hip", "jtp_propagate.hip", "jtp_readout.hip", "jtp_sample.hip", "jtp_profile.cpp", "jtp_comm.cpp"]
-SOURCES = ["jtp_plan.cpp"] + ENGINE + INST       # (compiled in parallel, one object each, then linked)
+# (the planner's units, pure host C++: csrc/jtp_plan_build.h has the map)
+PLANNER = ["jtp_plan.cpp", "jtp_plan_layout.cpp", "jtp_plan_loops.cpp", "jtp_plan_tasks.cpp", "jtp_plan_schedule.cpp", "jtp_plan_json.cpp"]
+SOURCES = PLANNER + ENGINE + INST                # (compiled in parallel, one object each, then linked)
 HEADERS = ["jtp_internal.h", "jtp_plan.h", "jtp_kernels.hip.h", "jtp_device.h", "jtp_engine.h", os.path.join("..", "..", "include", "jtprop.h")]
-DEPS = SOURCES + HEADERS
+PLANNER_HEADERS = ["jtp_plan.h", "jtp_plan_build.h", "jtp_internal.h", os.path.join("..", "..", "include", "jtprop.h")]
+DEPS = SOURCES + HEADERS + ["jtp_plan_build.h"]
 
 
 ID_FILE = os.path.join(LIBDIR, "BUILD_ID")
@@ -70,11 +73,12 @@ def build(force=False, verbose=True, extra=(), out=None, jobs=None):
              '-DJTP_SOURCE_ID="%s"' % sid] + list(extra)
     objdir = tempfile.mkdtemp(prefix="jtprop_build_")
     # objects of translation units whose sources did not change are taken from a cache beside the library (git-ignored):
-    # a planner-only change recompiles jtp_plan.cpp and the engine's units, not the kernel instantiation units
+    # a change to one planner unit recompiles that unit alone; one to the planner's face (jtp_plan.h) the planner and the engine's units,
+    # never the kernel instantiation units
     cache = os.path.join(LIBDIR, "objcache")
     os.makedirs(cache, exist_ok=True)
     import hashlib
-    headers = {"jtp_plan.cpp": ["jtp_plan.h", "jtp_internal.h", os.path.join("..", "..", "include", "jtprop.h")]}
+    headers = dict((src, PLANNER_HEADERS) for src in PLANNER)
     headers.update((src, HEADERS) for src in ENGINE)       # (every engine unit: all of them, the simplest rule that is right)
     try:                       # (the compiler is part of what an object is made of: a toolchain upgrade must not link old objects)
         toolchain = subprocess.check_output([hipcc, "--version"], stderr=subprocess.STDOUT)
@@ -112,7 +116,7 @@ def build(force=False, verbose=True, extra=(), out=None, jobs=None):
         # (the template translation units take 1-2 GiB of compiler each: at most eight at once, JTP_BUILD_JOBS overrides)
         jobs = jobs or int(os.environ.get("JTP_BUILD_JOBS", 0)) or max(1, min(len(SOURCES), os.cpu_count() or 2, 8))
         with ThreadPoolExecutor(jobs) as pool:
-            objs = list(pool.map(compile_one, INST + ENGINE + ["jtp_plan.cpp"]))
+            objs = list(pool.map(compile_one, INST + ENGINE + PLANNER))
         # link beside the target and move the result into place: a process that has the old library mapped keeps it,
         # nobody ever sees a half-written one
         tmp_out = out + ".tmp%d" % os.getpid()

@@ -306,4 +306,9 @@ int jtp_plan_marginal_task(const HostPlan &hp, int pnode, const std::vector<std:
 int jtp_plan_belief_task(const HostPlan &hp, int pnode, JtTask &task, std::vector<int32_t> &itab,
                          std::vector<JtBlock> &blocks, std::string &err);
 
+// Requests on ONE clique share passes over its table: request i of clique cliques[i] goes to the clique's group that still has room, at
+// most `per_group` requests each (`one_each`: a group per request - multi-set plans); cliques[i] < 0: request i is in no group.
+// Groups in the order of their first request, requests in order within a group.
+std::vector<std::vector<int>> jtp_group_requests(const int32_t *cliques, int n, int per_group, bool one_each);
+
 void jtp_plan_to_json(HostPlan &hp, bool with_tasks);

@@ -276,22 +276,13 @@ static int make_marg_batch(jtp_plan *pl, const std::vector<int32_t> &key, int32_
     // clique for two or three factor marginals: round 3 read the table once per request - config 3: 1831 reads of 878
     // tables, 2.1 x the bytes).  Multi-set plans marginalise psi x messages directly and keep one request per task.
     std::vector<char> lean_later;                        // per task: a unit clique's marginals (single-set plans)
-    std::vector<std::vector<int>> groups;
-    {
-        std::map<int, int> open;                         // clique -> its group that still has room
-        for (int i = 0; i < n; ++i) {
-            const int clique = cliques[i];
-            if (clique < 0 || clique >= hp.n_cliques) return set_err(JTP_EINVAL, "request %d: node %d is not a clique", i, clique);
-            if (!(hp.pn[clique].owner == hp.rank || hp.pn[clique].owner == hp.n_ranks)) return set_err(JTP_EINVAL, "clique %d belongs to rank %d", clique, hp.pn[clique].owner);
-            auto it = open.find(clique);
-            // (multi-set plans: one request per pass; unit cliques of single-set plans share passes like everybody else)
-            if (pl->multiset || it == open.end() || (int)groups[it->second].size() >= hp.knobs.marg_group) {
-                open[clique] = (int)groups.size();
-                groups.push_back(std::vector<int>());
-            }
-            groups[open[clique]].push_back(i);
-        }
+    for (int i = 0; i < n; ++i) {
+        const int clique = cliques[i];
+        if (clique < 0 || clique >= hp.n_cliques) return set_err(JTP_EINVAL, "request %d: node %d is not a clique", i, clique);
+        if (!(hp.pn[clique].owner == hp.rank || hp.pn[clique].owner == hp.n_ranks)) return set_err(JTP_EINVAL, "clique %d belongs to rank %d", clique, hp.pn[clique].owner);
     }
+    // (multi-set plans: one request per pass; unit cliques of single-set plans share passes like everybody else)
+    const std::vector<std::vector<int>> groups = jtp_group_requests(cliques, n, hp.knobs.marg_group, pl->multiset);
     for (const std::vector<int> &grp : groups) {
         const int clique = cliques[grp[0]];
         std::vector<std::vector<int>> ovs;

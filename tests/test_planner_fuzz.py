@@ -1,8 +1,12 @@
 """ASan + UBSan build of the host planner (pure C++, no HIP) driven by a descriptor fuzzer: random junction
 trees, half of them damaged (cycles, CSR offsets, unknown variables, owners, sizes ...).  jtp_build_plan must
 plan or refuse with a message - never crash or touch memory it does not own (sanitizers on
-the host library; the GPU pool has no GPU AddressSanitizer)."""
+the host library; the GPU pool has no GPU AddressSanitizer).  Accepted plans go on through the read-out entry points
+(jtp_plan_belief_task, jtp_plan_marginal_task); about half of the descriptors with covered variables name marginals to
+fold into the propagate.  The corpus must reach every kind of plan the harness counts."""
+import glob
 import os
+import re
 import shutil
 import subprocess
 
@@ -16,9 +20,14 @@ def test_planner_under_asan_ubsan_with_fuzzed_descriptors(tmp_path):
     exe = str(tmp_path / "fuzz_plan")
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
                            os.path.join(ROOT, "tests", "fuzz", "fuzz_plan.cpp"),
-                           os.path.join(ROOT, "junction-tree_amd", "csrc", "jtp_plan.cpp"), "-o", exe])
+                           *sorted(glob.glob(os.path.join(ROOT, "junction-tree_amd", "csrc", "jtp_plan*.cpp"))), "-o", exe])
     for seed in (12345, 7):
-        out = subprocess.run([exe, "2500", str(seed)], capture_output=True, text=True, timeout=600,
+        out = subprocess.run([exe, "2500", str(seed), "digest"], capture_output=True, text=True, timeout=600,
                              env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
         assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
         assert "planned" in out.stdout and "rejected with a message" in out.stdout
+        counts = re.search(r"plans with: (.*)", out.stdout).group(1)
+        reached = {m.group(1): int(m.group(2)) for m in re.finditer(r"([a-z\- ]+?) (\d+)(?:, |$)", counts)}
+        assert set(reached) == {"fold tasks", "reduce tasks", "mixed-radix rows", "unit tasks", "exchange steps", "multi-set", "scaled"}, counts
+        assert all(n > 0 for n in reached.values()), "seed %d: the corpus never reached %s" % (
+            seed, [k for k, n in reached.items() if n == 0])
