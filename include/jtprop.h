@@ -292,6 +292,28 @@ int jtp_get_log_z(jtp_plan *plan, int32_t batch, double *log_abs_z, int32_t *sig
  * of such (clique, sample) pairs and the first clique. */
 int jtp_sample(jtp_plan *plan, int32_t batch, int32_t n_samples, uint64_t seed, int32_t *states);
 
+/* The most probable joint assignment of every evidence set in [batch_begin, batch_end), by a max-product sweep over the clique
+ * potentials on the device: states[(b - batch_begin) * n_vars + v] = state of variable v for set b (a variable of no clique: 0),
+ * log_value (NULL, or [batch_end - batch_begin]) = log max_x prod_c psi_c(x) over the assignments x that agree with the set's evidence
+ * (jtp_set_evidence as last called - no propagate is needed, and the beliefs and messages one left are not touched); log_value less
+ * jtp_get_log_z of the set is the assignment's log posterior probability.
+ * The sweep runs over the tree as the description gave it, on the schedule of jtp_sample (by depth, then clique number; K_c = the
+ * variables clique c shares with its parent clique, F_c the others in host axis order, R_c = prod card(F_c)).  Upward, deepest first:
+ * for every assignment k of K_c, raw_c[k] = max over r in [0, R_c) of w(k, r) = ((double)psi_c[k, r] * m_1) * m_2 ... - the children
+ * of c in ascending clique number, float64, left to right - and arg_c[k] = the SMALLEST such r (C order over F_c); m_d =
+ * ldexp(raw_d[k_d], -e_d), e_d = ilogb(max raw_d): every message is read divided by a power of two that puts its largest entry in
+ * [1, 2), so nothing overflows whatever the depth (JTP_SCALED is not needed and changes nothing).  Entries that contradict the
+ * evidence are not looked at; raw_c[k] = 0 where k does.  Downward, every clique reads arg_c at the digits the cliques above wrote.
+ * log_value = log(max raw_root) + ln 2 * (sum of e_c over the other cliques).  Nothing depends on the plan's layout or launch flags:
+ * equal potentials and evidence give equal states, ties included.  All sets of a chunk go through the same launches (one per depth);
+ * a chunk is as many sets as keep the raw and arg tables - 12 bytes per assignment of K_c, summed over the cliques - under 64 MiB.
+ * Works on plans of one set, of n_batch sets and with JTP_SHARE_POTENTIALS, float32 and float64 tables, any layout.
+ * JTP_EUNSUPPORTED: JTP_MULTISET plans, n_ranks > 1, plans in which a clique keeps no table (cover_*).  A set FAILS where an entry
+ * that agrees with its evidence is negative or NaN, or where a clique's largest raw entry is zero or not finite (evidence of
+ * probability zero): its states are all -1, its log_value -inf; every set of the range is still written, the call returns JTP_EINVAL
+ * and the message names the number of failed sets and the first. */
+int jtp_map(jtp_plan *plan, int32_t batch_begin, int32_t batch_end, int32_t *states, double *log_value);
+
 /* Expected counts: the weighted sum over evidence sets [batch_begin, batch_end) of the NORMALISED marginals of a request list
  * (requests as in jtp_get_marginals), formed and accumulated on the device:
  *     host[out_off[i] + h] = sum_b  weights[b - batch_begin] * m_bi[h] / S_bi ,   S_bi = sum_h m_bi[h]
@@ -336,7 +358,8 @@ int jtp_get_launch_ms(jtp_plan *plan, double *ms, int32_t n);
 int jtp_debug_read_msg(jtp_plan *plan, int32_t batch, int64_t off, int64_t n, double *host);
 /* Test hooks.  knob "flow_debug": JtFlow::dbg of the following propagates (8 = every dataflow wait times
  * out after 20 ms: exercises the fall-back to one launch per level); "flow": 0 = launch per level from now on;
- * "fail_alloc": see jtp_debug_live_bytes; "acc_chunk": evidence sets per chunk of jtp_accumulate_marginals (0: by size). */
+ * "fail_alloc": see jtp_debug_live_bytes; "acc_chunk": evidence sets per chunk of jtp_accumulate_marginals (0: by size);
+ * "map_chunk": the same of jtp_map; "map_seg": entries of r a wave of jtp_map takes (0: the default; the result does not depend on it). */
 int jtp_debug_set(jtp_plan *plan, const char *knob, int64_t value);
 /* Test hook: bytes of device memory and of pinned host memory the library holds right now, process-wide (every plan's buffers;
  * either pointer may be NULL).  With knob "fail_alloc" of jtp_debug_set (the N-th allocation of the plan from now on reports

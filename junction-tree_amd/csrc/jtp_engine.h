@@ -3,6 +3,7 @@
 //   jtp_upload.hip     potentials in (pack, evaluate, synthetic fill), evidence, the active lists of multi-set plans
 //   jtp_propagate.hip  kernel tables and the one launch path, the flight board, jtp_propagate, jtp_sync, check_flow / settle
 //   jtp_readout.hip    beliefs, marginals, scale / Z / log Z, expected counts;    jtp_sample.hip   jtp_sample
+//   jtp_map.hip        jtp_map: the most probable assignment (max-product sweep over the potentials)
 //   jtp_profile.cpp    profiling, regions, statistics;    jtp_comm.cpp   RCCL and roctx loaders, jtp_comm_*, the exchange steps
 // Every global has one definition, in the unit that owns it; the other units reach it through the functions declared here.
 #pragma once
@@ -125,6 +126,41 @@ struct MargBatch {
     explicit MargBatch(MemLedger *m) : d_descs_fold(m), d_tasks(m), d_blocks(m), d_itab(m), d_descs(m), scratch(m), stage(m), acc(m) {}
 };
 
+// jtp_map (jtp_map.hip): one record per clique of the sampling schedule (HostPlan::sample, visit order), read by the kernels as it
+// stands.  v[0, nK): the variables shared with the parent clique, `radix` their C-order weight in the clique's raw / arg table of nk
+// entries; v[nK, nK + nF): the others, `radix` their weight in r.  A clique of many entries per k is cut into `nseg` contiguous
+// segments of r, a wave each, whose (max, first r) jt_map_merge puts together: the result does not depend on the cut.
+struct JtMap {
+    int64_t psi_off;                 // element offset of the clique's table in the potential arena
+    int64_t raw_off;                 // the clique's place in a set's raw / arg tables (entries)
+    int64_t part_off;                // ... and, nseg > 1, in a set's tables of segment results (entry k * nseg + seg)
+    int32_t nK, nF;
+    uint32_t R, nk;                  // products of the cardinalities of F and of K
+    uint32_t nseg;
+    int32_t ord;                     // place in the visit order: the slot of the clique's maximum
+    int32_t child_begin, child_end;  // the clique's children: a range of the JtMapChild array
+    JtSampleVar v[JT_MAX_VARS];
+};
+struct JtMapChild {
+    int64_t raw_off;                 // the child's place in a set's raw table
+    int32_t ord;                     // the child's record
+    int32_t pad;
+    uint32_t stride[JT_MAX_VARS];    // per variable v[j] of the PARENT's record: its weight in the child's k (0: not shared with the child)
+};
+// what jtp_map keeps with the plan: the records (built once) and the work area of one chunk of evidence sets (grow-only) - per set
+// the raw and arg tables, the segment results, the cliques' maxima as bit patterns, the evidence row, the state row, a flag
+struct MapMem {
+    DeviceBuf<JtMap> recs;
+    DeviceBuf<JtMapChild> kids;
+    DeviceBuf<int32_t> depth_begin;  // records [depth_begin[d], depth_begin[d + 1]) are depth d
+    DeviceBuf<char> work;
+    int64_t sets = 0;                // evidence sets `work` has room for
+    int64_t entries = 0, parts = 0;  // per set: raw / arg entries, segment results
+    std::vector<int64_t> depth_items;    // per depth: most (k, segment) pairs of a clique
+    std::vector<char> depth_merge;       // ... and whether some clique there is cut into segments
+    explicit MapMem(MemLedger *m) : recs(m), kids(m), depth_begin(m), work(m) {}
+};
+
 // what one evidence set of a single-set plan owns (multi-set plans: entry 0 holds the shared psi and the belief scratch)
 struct SetMem {
     DeviceBuf<char> psi, bel;
@@ -232,6 +268,13 @@ struct jtp_plan {
     // evidence sets per chunk as jtp_debug_set "acc_chunk" asks (0: as many as fit 64 MiB of partial copies)
     std::vector<hipEvent_t> acc_ev;
     int64_t acc_chunk = 0;
+    // jtp_map: the observed state of every variable in every evidence set as jtp_set_evidence was last given it ([set * n_vars + v],
+    // -1: not observed; empty: no call yet), the records and the work area, and the sets per chunk jtp_debug_set "map_chunk" asks
+    // for (0: as many as fit 64 MiB)
+    std::vector<int32_t> ev_obs;
+    MapMem map{&mem};
+    int64_t map_chunk = 0;
+    int64_t map_seg = 0;            // jtp_debug_set "map_seg": entries per segment of r (0: JT_MAP_SEG); setting it drops the records
     hipStream_t eval_stream = nullptr;   // stream whose kernels may still read the buffer
     bool eval_pending = false;
     int esize = 4;
@@ -251,6 +294,10 @@ __device__ __forceinline__ uint64_t jt_splitmix64(uint64_t x) {
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
     return z ^ (z >> 31);
+}
+// element offset of digit `digit` of a variable in a stored table (JtSampleVar, jtp_plan.h): jtp_sample.hip, jtp_map.hip
+__device__ __forceinline__ uint32_t jt_sample_at(const JtSampleVar &v, int digit) {
+    return ((uint32_t)digit & ((1u << v.lb) - 1u)) * v.stride + ((uint32_t)digit >> v.lb) * v.stride2;
 }
 #endif
 

@@ -22,9 +22,6 @@
 // set to -1, a clique that finds -1 among its conditioning digits fails without loading anything, and fail[0] counts the failed
 // (clique, sample) pairs, fail[1] keeps the smallest visit-order place among them.
 #define JT_SAMPLE_SALT 0x53414D504C45ull
-__device__ __forceinline__ uint32_t jt_sample_at(const JtSampleVar &v, int digit) {
-    return ((uint32_t)digit & ((1u << v.lb) - 1u)) * v.stride + ((uint32_t)digit >> v.lb) * v.stride2;
-}
 
 template <typename T>
 __global__ __launch_bounds__(256) void jt_sample_level(const JtSample *__restrict__ recs, const T *__restrict__ bel, int32_t *__restrict__ states,

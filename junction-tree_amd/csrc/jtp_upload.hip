@@ -580,6 +580,10 @@ int jtp_set_evidence(jtp_plan *pl, int32_t batch, int32_t n, const int32_t *var_
     }
     HIP_TRY(hipMemcpy(b.ev, ev.data(), ev.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     b.ev_any = n > 0;
+    // (the host's copy, by variable: jtp_map uploads the rows of the sets it works on)
+    if (pl->ev_obs.empty()) pl->ev_obs.assign((size_t)hp.n_batch * (size_t)hp.n_vars, -1);
+    std::fill_n(pl->ev_obs.begin() + (size_t)batch * (size_t)hp.n_vars, (size_t)hp.n_vars, -1);
+    for (int i = 0; i < n; ++i) pl->ev_obs[(size_t)batch * (size_t)hp.n_vars + (size_t)var_ids[i]] = states[i];
     if (pl->multiset) {
         // a group of evidence sets may sum the elements of a vector before the message product on a clique while none of ITS
         // sets observes a variable on that clique's element bits (JtTask::esum_groups; bit b stands for the groups g = b mod 64)

@@ -436,6 +436,30 @@ class Plan:
         _capi.check(rc)
         return out
 
+    def map(self, batch_begin=0, batch_end=None):
+        """The most probable joint assignment of every evidence set in [batch_begin, batch_end) (`jtp_map`): an int32 array
+        (n_sets, len(self.var_labels)), column j the state of variable `self.var_labels[j]`, and a float64 array (n_sets,) of
+        log max_x prod psi(x), the unnormalised log value of that assignment - less `log_z(batch)[1]` it is the assignment's log
+        posterior probability.  A max-product sweep over the staged potentials on the device, all sets through the same launches: no
+        propagate is needed, and what one left is not touched.  The evidence is what `set_evidence` last gave each set; observed
+        variables come out in their observed state.  Among assignments of equal value the sweep's tie rule decides (include/jtprop.h),
+        whatever the plan's layout.
+
+        Where sets have no assignment of positive finite value (evidence of probability zero, negative entries) `_capi.JtpError` is
+        raised; its `states` and `log_value` attributes hold the arrays, with -1 and -inf for those sets."""
+        end = self.n_batch if batch_end is None else int(batch_end)
+        begin = int(batch_begin)
+        n_sets = max(end - begin, 0)
+        states = np.zeros((n_sets, len(self.var_labels)), dtype=np.int32)
+        value = np.zeros(n_sets, dtype=np.float64)
+        rc = self._lib.jtp_map(self._handle, begin, end, states.ctypes.data_as(C.c_void_p), value.ctypes.data_as(C.c_void_p))
+        if rc == _capi.JTP_EINVAL and n_sets > 0 and bool(np.isneginf(value).any()):
+            err = _capi.JtpError(self._lib.jtp_last_error().decode("utf-8", "replace"))
+            err.states, err.log_value = states, value
+            raise err
+        _capi.check(rc)
+        return states, value
+
     def accumulate_marginals(self, requests, weights=None, batch_begin=0, batch_end=None):
         """Expected counts (`jtp_accumulate_marginals`): for `requests` = [(clique, labels), ...] the sum over the evidence sets
         [batch_begin, batch_end) of `weights[b - batch_begin]` x the marginal `marginals(requests, batch=b)` would return, each

@@ -320,6 +320,68 @@ class JunctionTree:
             out.setdefault(lab, np.zeros(int(n), dtype=np.int32))
         return out
 
+    def map(self, values, evidence=None):
+        """The most probable joint assignment under the distribution the factor values define (not in the reference, which stops
+        at marginals): ({variable: state}, log_value), log_value = log of the product of the factor values at that assignment -
+        less log Z (`propagate(values, normalize=True)`, then `tree.log_z`) it is the assignment's log probability.  `evidence`:
+        {variable: observed state} - the most probable explanation of that observation.  See `map_evidence_sets`."""
+        states, value = self.map_evidence_sets(values, [dict(evidence) if evidence else {}])
+        return {lab: int(col[0]) for lab, col in states.items()}, float(value[0])
+
+    def map_evidence_sets(self, values, evidence_sets):
+        """`map` for several evidence sets over the same factor values: ({variable: int32 array of length n_sets}, float64 array of
+        the sets' log values), all sets through the same launches of one max-product sweep on the device (`engine.Plan.map`) over
+        one copy of the clique tables.  Models whose Z lies beyond float64 need nothing special: the sweep rescales its messages
+        by powers of two and reports a logarithm.  A set whose evidence has probability zero raises `_capi.JtpError`, carrying
+        `states` (-1 for that set) and `log_value` (-inf) as `engine.Plan.map` does.
+
+        The sweep reads every clique table, so every clique table is materialised: the plan is made without `cover`, unlike
+        `propagate`'s.  On lattice-like models, whose cliques are mostly variables no factor of theirs covers, that is many times the
+        memory - 9 GiB for the 6 x 167 lattice of cardinality 8 (BASELINE configs[2]) against the few MiB `propagate` needs."""
+        import weakref
+        from . import engine
+
+        ct = self.clique_tree
+        sizes = ct.factor_graph.sizes
+        n_sets = len(evidence_sets)
+        if n_sets == 0:
+            return {lab: np.zeros(0, dtype=np.int32) for lab in sizes}, np.zeros(0)
+        all_f32 = all(type(x) is np.ndarray and x.dtype == np.float32 for x in values)
+        dtype = "f32" if all_f32 else "f64"
+        # (an entry of its own, as `sample` keeps: what `propagate(xs, changed=...)` trusts about "plan" is never said of this plan)
+        mark = (dtype, n_sets, tuple(sizes.items()), tuple(sorted(self._opts.items())))
+        hit = self._memo.get("plan_map")
+        plan = engine.cached_plan(hit[1], hit[2]()) if hit is not None and hit[0] == mark else None
+        if plan is None:
+            node_vars = [list(c) for c in ct.maxcliques] + [list(s) for s in self.separators]
+            plan, key = engine.plan_for(self.tree, node_vars, sizes, dtype, return_key=True, n_batch=n_sets, share_potentials=True, **self._opts)
+            self._memo["plan_map"] = (mark, key, weakref.ref(plan))
+        _stage_changed_cliques(plan, ct, values)
+        try:
+            for b, observed in enumerate(evidence_sets):
+                plan.set_evidence(dict(observed) if observed else {}, batch=b)
+            try:
+                states, value = plan.map(0, n_sets)
+            except Exception as exc:
+                if hasattr(exc, "states"):
+                    exc.states = self._map_columns(plan, exc.states, sizes)
+                raise
+        finally:
+            for b, observed in enumerate(evidence_sets):     # (the plan is the cache's: whoever is handed it next finds no evidence set)
+                if observed:
+                    plan.set_evidence({}, batch=b)
+        return self._map_columns(plan, states, sizes), value
+
+    @staticmethod
+    def _map_columns(plan, states, sizes):
+        out = {lab: states[:, j] for j, lab in enumerate(plan.var_labels)}
+        zeros = np.where(states[:, :1].reshape(-1) < 0, -1, 0).astype(np.int32) if states.shape[1] else np.zeros(len(states), dtype=np.int32)
+        for lab in plan._trivial:                            # (one-state variables the plan keeps on the host)
+            out[lab] = zeros
+        for lab in sizes:                                    # (variables of no clique cannot occur: every variable is in a factor)
+            out.setdefault(lab, zeros)
+        return out
+
     def propagate_evidence_sets(self, xs, evidence_sets, normalize=False):
         """`propagate` for several hard-evidence sets over the same factor values (no counterpart in the
         reference, whose users loop over `propagate` after slicing the factors, `README.md:155-165`):
