@@ -314,6 +314,31 @@ int jtp_sample(jtp_plan *plan, int32_t batch, int32_t n_samples, uint64_t seed, 
  * and the message names the number of failed sets and the first. */
 int jtp_map(jtp_plan *plan, int32_t batch_begin, int32_t batch_end, int32_t *states, double *log_value);
 
+/* The joint of n_query distinct variables that need not share a clique, from the beliefs of the last propagate of evidence set
+ * `batch`: host[] = the table over var_ids[0 .. n_query) in that axis order (doubles, C order).  Unnormalised in the sense of
+ * jtp_get_marginal: it sums to Z, and on a JTP_SCALED plan it is the true table times 2^-E, E the exponent of the TOP clique below
+ * (*log2_scale, if not NULL; what jtp_get_log2_scale reports for that clique; 0 without the flag).
+ * The sweep runs over the tree as the description gave it, on the schedule of jtp_sample (by depth, then clique number; K_c = the
+ * variables clique c shares with its parent clique, F_c the others in host axis order, R_c = prod card(F_c)).  The home of a query
+ * variable is the shallowest clique that holds it; the top is the deepest clique whose subtree holds every home; only the cliques on
+ * the paths from the homes up to the top are read.  With C_c = the query variables whose home lies in the subtree of c (in the
+ * order of the query), Q_c those whose home is c, and r' running over the R'_c assignments of F_c without Q_c: upward, deepest
+ * first, for every such clique but the top, every assignment k of K_c and x of C_c,
+ *     sigma_c[k] = sum_r beta_c[k, r],   U_c[k, x] = sum_r' ((double)beta_c[k, x|Q_c, r'] * M_d1[.]) * M_d2[.] ...,
+ *     M_c[k, x] = U_c[k, x] / sigma_c[k]   (0 where sigma_c[k] = 0)
+ * - d1 < d2 < ... the children of c on those paths in ascending clique number, float64, left to right, each read at the digits of
+ * K_d that (k, x, r') fix and at x restricted to C_d.  The top forms the same sum over all its variables outside the query, K_top
+ * included, and does not divide.  A sum of n terms is added in an order that depends on n alone, so nothing depends on the plan's
+ * layout, compaction, root or launch flags: equal beliefs give bit-equal joints.  The power of two a JTP_SCALED plan keeps per clique
+ * cancels in U / sigma.  Observed variables need nothing special (the joint is zero off an observed state), evidence of probability
+ * zero gives a joint of zeros and JTP_OK, and where every variable lies in one clique the result is that clique's marginal.
+ * JTP_EINVAL: n_query < 1, a variable listed twice, out of range or of no clique, an evidence set never propagated.
+ * JTP_EUNSUPPORTED, with the reason: JTP_MULTISET plans, n_ranks > 1, plans in which a clique keeps no table (cover_*); more than 16
+ * variables; a result, or the sigma and M tables of a call together, beyond 64 MiB (the message names the clique that passes it and
+ * the size of its M).  Where a belief entry read is negative or NaN, or a sum is not finite (tables that overflowed), the joint is
+ * still written, the call returns JTP_EINVAL and the message names the number of such (clique, k) pairs and the first clique. */
+int jtp_joint(jtp_plan *plan, int32_t batch, int32_t n_query, const int32_t *var_ids, double *host, int64_t *log2_scale);
+
 /* Expected counts: the weighted sum over evidence sets [batch_begin, batch_end) of the NORMALISED marginals of a request list
  * (requests as in jtp_get_marginals), formed and accumulated on the device:
  *     host[out_off[i] + h] = sum_b  weights[b - batch_begin] * m_bi[h] / S_bi ,   S_bi = sum_h m_bi[h]

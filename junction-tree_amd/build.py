@@ -16,7 +16,7 @@ LIB = os.path.join(LIBDIR, "libjtprop.so")
 # (longest compile first: a worker that frees up takes the next unit in this order, so the short ones fill in at the end)
 INST = ["jtp_inst_%s_%s.hip" % (fam, t) for fam in ("both", "bothm", "level", "mixc", "mix", "flow", "multi", "shape") for t in ("f32", "f64")]
 # (the engine's units, by concern: csrc/jtp_engine.h has the map)
-ENGINE = ["jtp_engine.hip", "jtp_upload.hip", "jtp_propagate.hip", "jtp_readout.hip", "jtp_sample.hip", "jtp_map.hip", "jtp_profile.cpp", "jtp_comm.cpp"]
+ENGINE = ["jtp_engine.hip", "jtp_upload.hip", "jtp_propagate.hip", "jtp_readout.hip", "jtp_sample.hip", "jtp_map.hip", "jtp_joint.hip", "jtp_profile.cpp", "jtp_comm.cpp"]
 # (the planner's units, pure host C++: csrc/jtp_plan_build.h has the map)
 PLANNER = ["jtp_plan.cpp", "jtp_plan_layout.cpp", "jtp_plan_loops.cpp", "jtp_plan_tasks.cpp", "jtp_plan_schedule.cpp", "jtp_plan_json.cpp"]
 SOURCES = PLANNER + ENGINE + INST                # (compiled in parallel, one object each, then linked)

@@ -4,6 +4,7 @@
 //   jtp_propagate.hip  kernel tables and the one launch path, the flight board, jtp_propagate, jtp_sync, check_flow / settle
 //   jtp_readout.hip    beliefs, marginals, scale / Z / log Z, expected counts;    jtp_sample.hip   jtp_sample
 //   jtp_map.hip        jtp_map: the most probable assignment (max-product sweep over the potentials)
+//   jtp_joint.hip      jtp_joint: the joint of variables of different cliques, from the beliefs a propagate left
 //   jtp_profile.cpp    profiling, regions, statistics;    jtp_comm.cpp   RCCL and roctx loaders, jtp_comm_*, the exchange steps
 // Every global has one definition, in the unit that owns it; the other units reach it through the functions declared here.
 #pragma once
@@ -161,6 +162,49 @@ struct MapMem {
     explicit MapMem(MemLedger *m) : recs(m), kids(m), depth_begin(m), work(m) {}
 };
 
+// jtp_joint (jtp_joint.hip): one record per ACTIVE clique of a query (the cliques on the paths from the query variables' homes up to
+// the top), in visit order - the top first - built and uploaded per call.  v[0, nK): the variables shared with the parent clique,
+// `radix` their C-order weight in k; v[nK, nK + nQ): the query variables whose home the clique is (their digits come from x);
+// v[nK + nQ, nK + nQ + nF): the clique's other variables in host axis order, `radix` their weight in r'.  f[0, nFs): ALL variables
+// the clique does not share with its parent, host axis order, `radix` their weight in r - what sigma sums over.  x[0, nX): the
+// query variables whose home lies in the clique's subtree, in the order of the query, `radix` their C-order weight in x; `slot` the
+// place in v of one whose home is this clique, -1 for one carried up from a child.  The top has nK = 0: the variables it shares
+// with its parent are among its "other" variables, summed over.
+#define JT_JOINT_MAXQ 16         // query variables of a call
+struct JtJointX {
+    int32_t card;
+    uint32_t radix;
+    int32_t slot;
+    int32_t pad;
+};
+struct JtJoint {
+    int64_t bel_off;                 // element offset of the clique's table in the belief arena
+    int64_t sig_off, msg_off;        // places of sigma_c[nk] and of M_c[nk * X] in the work area (doubles); the top: msg_off = the result's
+    int64_t part_off;                // nseg > 1: place of the segment sums (entry (k * X + x) * nseg + segment)
+    int32_t nK, nQ, nF, nFs, nX;
+    int32_t lanes;                   // lanes that share one output entry: min(64, R' rounded up to a power of two)
+    uint32_t R, Rp, nk, X;           // prod card of f (R_c), of the "other" variables (R'_c), of K_c, of x (C_c)
+    uint32_t nseg;                   // contiguous segments the sum over r' is cut into, a wave each (a function of R'_c alone)
+    int32_t ord;                     // place in the visit order of the sampling schedule (the failure report keeps the smallest)
+    int32_t top;
+    int32_t child_begin, child_end;  // the clique's ACTIVE children, ascending clique number: a range of the JtJointChild array
+    JtSampleVar v[JT_MAX_VARS];
+    JtSampleVar f[JT_MAX_VARS];
+    JtJointX x[JT_JOINT_MAXQ];
+};
+struct JtJointChild {
+    int64_t msg_off;                 // the child's M in the work area
+    uint32_t stride[JT_MAX_VARS];    // per variable v[j] of the PARENT's record: its weight in the child's message index (0: not in K_d)
+    uint32_t xstride[JT_JOINT_MAXQ]; // per x[i] of the parent's record: its weight there (0: not carried by this child)
+};
+// what jtp_joint keeps with the plan, grow-only: the records of the last call (JtJoint, then JtJointChild) and the work area - the
+// failure report (count, smallest visit-order place, the top's flag), every sigma, M and segment sum, the result
+struct JointMem {
+    DeviceBuf<char> recs;
+    DeviceBuf<double> work;
+    explicit JointMem(MemLedger *m) : recs(m), work(m) {}
+};
+
 // what one evidence set of a single-set plan owns (multi-set plans: entry 0 holds the shared psi and the belief scratch)
 struct SetMem {
     DeviceBuf<char> psi, bel;
@@ -275,6 +319,7 @@ struct jtp_plan {
     MapMem map{&mem};
     int64_t map_chunk = 0;
     int64_t map_seg = 0;            // jtp_debug_set "map_seg": entries per segment of r (0: JT_MAP_SEG); setting it drops the records
+    JointMem joint{&mem};           // jtp_joint: records and work area
     hipStream_t eval_stream = nullptr;   // stream whose kernels may still read the buffer
     bool eval_pending = false;
     int esize = 4;
@@ -295,7 +340,7 @@ __device__ __forceinline__ uint64_t jt_splitmix64(uint64_t x) {
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
     return z ^ (z >> 31);
 }
-// element offset of digit `digit` of a variable in a stored table (JtSampleVar, jtp_plan.h): jtp_sample.hip, jtp_map.hip
+// element offset of digit `digit` of a variable in a stored table (JtSampleVar, jtp_plan.h): jtp_sample.hip, jtp_map.hip, jtp_joint.hip
 __device__ __forceinline__ uint32_t jt_sample_at(const JtSampleVar &v, int digit) {
     return ((uint32_t)digit & ((1u << v.lb) - 1u)) * v.stride + ((uint32_t)digit >> v.lb) * v.stride2;
 }

@@ -460,6 +460,36 @@ class Plan:
         _capi.check(rc)
         return states, value
 
+    def joint(self, variables, batch=0):
+        """The joint of `variables` - distinct labels that need not share a clique - from the beliefs of the last propagate of evidence
+        set `batch` (`jtp_joint`): (float64 array with one axis per variable, in the order given, log2_scale).  Unnormalised, as
+        `marginal` is: it sums to Z, and on a `scaled` plan it is the true table times 2**-log2_scale (0 on other plans).  Only the
+        cliques between the variables are read, upward to the deepest clique that has all of them below it; observed variables
+        are zero off their observed state, and evidence of probability zero gives a table of zeros.  Equal beliefs give bit-equal
+        tables whatever the plan's layout.
+
+        Where a belief entry read is negative or NaN or a sum is not finite (tables that overflowed on a plan made without `scaled`)
+        `_capi.JtpError` is raised; its `joint` attribute holds the table as it came out."""
+        variables = list(variables)
+        unknown = [lab for lab in variables if lab not in self.var_id and lab not in self._trivial]
+        if unknown:
+            raise ValueError("variable %r is in no clique of the plan" % (unknown[0],))
+        if len(set(variables)) != len(variables):
+            raise ValueError("a variable is listed twice: %r" % (variables,))
+        shape = tuple(1 if lab in self._trivial else self.card[self.var_id[lab]] for lab in variables)
+        ids = [self.var_id[lab] for lab in variables if lab not in self._trivial]
+        out = np.zeros(shape, dtype=np.float64)
+        e = C.c_int64(0)
+        rc = self._lib.jtp_joint(self._handle, int(batch), len(ids), C.cast(_int_array(ids), C.c_void_p), out.ctypes.data_as(C.c_void_p), C.byref(e))
+        if rc == _capi.JTP_EINVAL:
+            msg = self._lib.jtp_last_error().decode("utf-8", "replace")
+            if "(clique, k) pairs" in msg:
+                err = _capi.JtpError(msg)
+                err.joint, err.log2_scale = out, int(e.value)
+                raise err
+        _capi.check(rc)
+        return out, int(e.value)
+
     def accumulate_marginals(self, requests, weights=None, batch_begin=0, batch_end=None):
         """Expected counts (`jtp_accumulate_marginals`): for `requests` = [(clique, labels), ...] the sum over the evidence sets
         [batch_begin, batch_end) of `weights[b - batch_begin]` x the marginal `marginals(requests, batch=b)` would return, each

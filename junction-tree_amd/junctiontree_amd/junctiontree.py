@@ -320,6 +320,62 @@ class JunctionTree:
             out.setdefault(lab, np.zeros(int(n), dtype=np.int32))
         return out
 
+    def joint(self, values, variables, evidence=None, normalize=False):
+        """The joint distribution of `variables` - a list of distinct variables that need not share a factor or a clique - under the
+        distribution the factor values define (not in the reference, which stops at the marginals of its factors): a float64 array
+        with one axis per variable, in the order given.  `evidence`: {variable: observed state} - the table is then that of the
+        posterior, zero off the observed state of an observed variable.  Without `normalize` the table is unnormalised, as the
+        marginals of `propagate` are: it sums to Z (times the probability of the evidence).  `normalize`: the propagate behind it
+        runs on an overflow-safe plan (`engine.Plan(scaled=True)`) and the table is divided by its sum - a probability table, also
+        where Z lies beyond float64; evidence of probability zero then raises `_capi.JtpError`.
+
+        One propagate, then one upward sweep on the device over the cliques between the variables (`engine.Plan.joint`), where
+        clamping one variable to each of its states in turn costs a propagate per state.
+
+        The sweep reads the clique beliefs, so every clique table is materialised: the plan is made without `cover`, unlike
+        `propagate`'s.  On lattice-like models, whose cliques are mostly variables no factor of theirs covers, that is many times the
+        memory - 9 GiB for the 6 x 167 lattice of cardinality 8 (BASELINE configs[2]) against the few MiB `propagate` needs."""
+        import weakref
+        from . import engine
+        from ._capi import JtpError
+
+        ct = self.clique_tree
+        sizes = ct.factor_graph.sizes
+        variables = list(variables)
+        for lab in variables:
+            if lab not in sizes:
+                raise ValueError("variable %r is not a variable of the model" % (lab,))
+        if len(set(variables)) != len(variables):
+            raise ValueError("a variable is listed twice: %r" % (variables,))
+        if not variables:
+            raise ValueError("at least one variable")
+        all_f32 = all(type(x) is np.ndarray and x.dtype == np.float32 for x in values)
+        dtype = "f32" if all_f32 else "f64"
+        # (an entry of its own, as `sample` keeps: what `propagate(xs, changed=...)` trusts about "plan" is never said of this plan)
+        memo = "plan_joint" + ("_scaled" if normalize else "")
+        mark = (dtype, tuple(sizes.items()), tuple(sorted(self._opts.items())))
+        hit = self._memo.get(memo)
+        plan = engine.cached_plan(hit[1], hit[2]()) if hit is not None and hit[0] == mark else None
+        if plan is None:
+            node_vars = [list(c) for c in ct.maxcliques] + [list(s) for s in self.separators]
+            extra = {"scaled": True} if normalize else {}
+            plan, key = engine.plan_for(self.tree, node_vars, sizes, dtype, return_key=True, **extra, **self._opts)
+            self._memo[memo] = (mark, key, weakref.ref(plan))
+        _stage_changed_cliques(plan, ct, values)
+        plan.set_evidence(dict(evidence) if evidence else {})
+        try:
+            plan.propagate(sync=False)
+            table, _ = plan.joint(variables)
+        finally:
+            if evidence:                                     # (the plan is the cache's: whoever is handed it next finds no evidence set)
+                plan.set_evidence({})
+        if normalize:
+            total = table.sum()
+            if not total > 0.0:
+                raise JtpError("joint: the table sums to %r - evidence of probability zero has no posterior to normalise" % (float(total),))
+            table = table / total
+        return table
+
     def map(self, values, evidence=None):
         """The most probable joint assignment under the distribution the factor values define (not in the reference, which stops
         at marginals): ({variable: state}, log_value), log_value = log of the product of the factor values at that assignment -
