@@ -20,7 +20,7 @@ ENGINE = ["jtp_engine.hip", "jtp_upload.hip", "jtp_propagate.hip", "jtp_readout.
 # (the planner's units, pure host C++: csrc/jtp_plan_build.h has the map)
 PLANNER = ["jtp_plan.cpp", "jtp_plan_layout.cpp", "jtp_plan_loops.cpp", "jtp_plan_tasks.cpp", "jtp_plan_schedule.cpp", "jtp_plan_json.cpp"]
 SOURCES = PLANNER + ENGINE + INST                # (compiled in parallel, one object each, then linked)
-HEADERS = ["jtp_internal.h", "jtp_plan.h", "jtp_kernels.hip.h", "jtp_device.h", "jtp_engine.h", os.path.join("..", "..", "include", "jtprop.h")]
+HEADERS = ["jtp_internal.h", "jtp_plan.h", "jtp_kernels.hip.h", "jtp_device.h", "jtp_engine.h", "jtp_query.h", os.path.join("..", "..", "include", "jtprop.h")]
 PLANNER_HEADERS = ["jtp_plan.h", "jtp_plan_build.h", "jtp_internal.h", os.path.join("..", "..", "include", "jtprop.h")]
 DEPS = SOURCES + HEADERS + ["jtp_plan_build.h"]
 

@@ -2,7 +2,9 @@
 //   jtp_engine.hip     errors, host memory, device queries, plan creation and destruction, zero_padding, jtp_debug_*
 //   jtp_upload.hip     potentials in (pack, evaluate, synthetic fill), evidence, the active lists of multi-set plans
 //   jtp_propagate.hip  kernel tables and the one launch path, the flight board, jtp_propagate, jtp_sync, check_flow / settle
-//   jtp_readout.hip    beliefs, marginals, scale / Z / log Z, expected counts;    jtp_sample.hip   jtp_sample
+//   jtp_readout.hip    beliefs, marginals, scale / Z / log Z, expected counts
+//   jtp_sample.hip     jtp_sample: joint posterior samples from the beliefs a propagate left        (these three: the queries on the sampling
+//                      schedule; jtp_query.h has their records and the table walk, child staging and launch shape they share)
 //   jtp_map.hip        jtp_map: the most probable assignment (max-product sweep over the potentials)
 //   jtp_joint.hip      jtp_joint: the joint of variables of different cliques, from the beliefs a propagate left
 //   jtp_profile.cpp    profiling, regions, statistics;    jtp_comm.cpp   RCCL and roctx loaders, jtp_comm_*, the exchange steps
@@ -17,6 +19,7 @@
 
 #include "jtp_device.h"
 #include "jtp_plan.h"
+#include "jtp_query.h"
 
 // ------------------------------------------------------------------------------------------ errors (jtp_engine.hip)
 
@@ -127,84 +130,6 @@ struct MargBatch {
     explicit MargBatch(MemLedger *m) : d_descs_fold(m), d_tasks(m), d_blocks(m), d_itab(m), d_descs(m), scratch(m), stage(m), acc(m) {}
 };
 
-// jtp_map (jtp_map.hip): one record per clique of the sampling schedule (HostPlan::sample, visit order), read by the kernels as it
-// stands.  v[0, nK): the variables shared with the parent clique, `radix` their C-order weight in the clique's raw / arg table of nk
-// entries; v[nK, nK + nF): the others, `radix` their weight in r.  A clique of many entries per k is cut into `nseg` contiguous
-// segments of r, a wave each, whose (max, first r) jt_map_merge puts together: the result does not depend on the cut.
-struct JtMap {
-    int64_t psi_off;                 // element offset of the clique's table in the potential arena
-    int64_t raw_off;                 // the clique's place in a set's raw / arg tables (entries)
-    int64_t part_off;                // ... and, nseg > 1, in a set's tables of segment results (entry k * nseg + seg)
-    int32_t nK, nF;
-    uint32_t R, nk;                  // products of the cardinalities of F and of K
-    uint32_t nseg;
-    int32_t ord;                     // place in the visit order: the slot of the clique's maximum
-    int32_t child_begin, child_end;  // the clique's children: a range of the JtMapChild array
-    JtSampleVar v[JT_MAX_VARS];
-};
-struct JtMapChild {
-    int64_t raw_off;                 // the child's place in a set's raw table
-    int32_t ord;                     // the child's record
-    int32_t pad;
-    uint32_t stride[JT_MAX_VARS];    // per variable v[j] of the PARENT's record: its weight in the child's k (0: not shared with the child)
-};
-// what jtp_map keeps with the plan: the records (built once) and the work area of one chunk of evidence sets (grow-only) - per set
-// the raw and arg tables, the segment results, the cliques' maxima as bit patterns, the evidence row, the state row, a flag
-struct MapMem {
-    DeviceBuf<JtMap> recs;
-    DeviceBuf<JtMapChild> kids;
-    DeviceBuf<int32_t> depth_begin;  // records [depth_begin[d], depth_begin[d + 1]) are depth d
-    DeviceBuf<char> work;
-    int64_t sets = 0;                // evidence sets `work` has room for
-    int64_t entries = 0, parts = 0;  // per set: raw / arg entries, segment results
-    std::vector<int64_t> depth_items;    // per depth: most (k, segment) pairs of a clique
-    std::vector<char> depth_merge;       // ... and whether some clique there is cut into segments
-    explicit MapMem(MemLedger *m) : recs(m), kids(m), depth_begin(m), work(m) {}
-};
-
-// jtp_joint (jtp_joint.hip): one record per ACTIVE clique of a query (the cliques on the paths from the query variables' homes up to
-// the top), in visit order - the top first - built and uploaded per call.  v[0, nK): the variables shared with the parent clique,
-// `radix` their C-order weight in k; v[nK, nK + nQ): the query variables whose home the clique is (their digits come from x);
-// v[nK + nQ, nK + nQ + nF): the clique's other variables in host axis order, `radix` their weight in r'.  f[0, nFs): ALL variables
-// the clique does not share with its parent, host axis order, `radix` their weight in r - what sigma sums over.  x[0, nX): the
-// query variables whose home lies in the clique's subtree, in the order of the query, `radix` their C-order weight in x; `slot` the
-// place in v of one whose home is this clique, -1 for one carried up from a child.  The top has nK = 0: the variables it shares
-// with its parent are among its "other" variables, summed over.
-#define JT_JOINT_MAXQ 16         // query variables of a call
-struct JtJointX {
-    int32_t card;
-    uint32_t radix;
-    int32_t slot;
-    int32_t pad;
-};
-struct JtJoint {
-    int64_t bel_off;                 // element offset of the clique's table in the belief arena
-    int64_t sig_off, msg_off;        // places of sigma_c[nk] and of M_c[nk * X] in the work area (doubles); the top: msg_off = the result's
-    int64_t part_off;                // nseg > 1: place of the segment sums (entry (k * X + x) * nseg + segment)
-    int32_t nK, nQ, nF, nFs, nX;
-    int32_t lanes;                   // lanes that share one output entry: min(64, R' rounded up to a power of two)
-    uint32_t R, Rp, nk, X;           // prod card of f (R_c), of the "other" variables (R'_c), of K_c, of x (C_c)
-    uint32_t nseg;                   // contiguous segments the sum over r' is cut into, a wave each (a function of R'_c alone)
-    int32_t ord;                     // place in the visit order of the sampling schedule (the failure report keeps the smallest)
-    int32_t top;
-    int32_t child_begin, child_end;  // the clique's ACTIVE children, ascending clique number: a range of the JtJointChild array
-    JtSampleVar v[JT_MAX_VARS];
-    JtSampleVar f[JT_MAX_VARS];
-    JtJointX x[JT_JOINT_MAXQ];
-};
-struct JtJointChild {
-    int64_t msg_off;                 // the child's M in the work area
-    uint32_t stride[JT_MAX_VARS];    // per variable v[j] of the PARENT's record: its weight in the child's message index (0: not in K_d)
-    uint32_t xstride[JT_JOINT_MAXQ]; // per x[i] of the parent's record: its weight there (0: not carried by this child)
-};
-// what jtp_joint keeps with the plan, grow-only: the records of the last call (JtJoint, then JtJointChild) and the work area - the
-// failure report (count, smallest visit-order place, the top's flag), every sigma, M and segment sum, the result
-struct JointMem {
-    DeviceBuf<char> recs;
-    DeviceBuf<double> work;
-    explicit JointMem(MemLedger *m) : recs(m), work(m) {}
-};
-
 // what one evidence set of a single-set plan owns (multi-set plans: entry 0 holds the shared psi and the belief scratch)
 struct SetMem {
     DeviceBuf<char> psi, bel;
@@ -303,11 +228,7 @@ struct jtp_plan {
     PinnedBuf<char> eval_host{&mem};     // pinned mirror of the same size: the caller's tables are copied here before the call returns
     size_t eval_cursor = 0;
     DeviceBuf<char> unit_scratch{&mem};  // scratch arena in which the belief of a unit clique is formed on demand (jtp_get_belief)
-    // jtp_sample: the records of the sampling schedule (HostPlan::sample, visit order), the state rows of one chunk of samples
-    // (int32[rows][n_vars], grow-only, reused chunk after chunk) and the failure report (count, smallest visit-order place)
-    DeviceBuf<JtSample> d_sample{&mem};
-    DeviceBuf<int32_t> sample_states{&mem};
-    DeviceBuf<unsigned long long> d_sample_fail{&mem};
+    SampleMem sample{&mem};         // jtp_sample: records, state rows, failure report
     // jtp_accumulate_marginals: an event per stream (the accumulation waits for the sets' formation launches), made on first use;
     // evidence sets per chunk as jtp_debug_set "acc_chunk" asks (0: as many as fit 64 MiB of partial copies)
     std::vector<hipEvent_t> acc_ev;
@@ -318,7 +239,7 @@ struct jtp_plan {
     std::vector<int32_t> ev_obs;
     MapMem map{&mem};
     int64_t map_chunk = 0;
-    int64_t map_seg = 0;            // jtp_debug_set "map_seg": entries per segment of r (0: JT_MAP_SEG); setting it drops the records
+    int64_t map_seg = 0;            // jtp_debug_set "map_seg": entries per segment of r (0: JT_QUERY_SEG); setting it drops the records
     JointMem joint{&mem};           // jtp_joint: records and work area
     hipStream_t eval_stream = nullptr;   // stream whose kernels may still read the buffer
     bool eval_pending = false;
@@ -339,10 +260,6 @@ __device__ __forceinline__ uint64_t jt_splitmix64(uint64_t x) {
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
     return z ^ (z >> 31);
-}
-// element offset of digit `digit` of a variable in a stored table (JtSampleVar, jtp_plan.h): jtp_sample.hip, jtp_map.hip, jtp_joint.hip
-__device__ __forceinline__ uint32_t jt_sample_at(const JtSampleVar &v, int digit) {
-    return ((uint32_t)digit & ((1u << v.lb) - 1u)) * v.stride + ((uint32_t)digit >> v.lb) * v.stride2;
 }
 #endif
 

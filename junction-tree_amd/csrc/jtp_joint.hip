@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "jtp_engine.h"
+#include "jtp_query.h"
 
 // jtp_joint works on the sampling schedule (HostPlan::sample: the caller's tree by depth, then clique number; K the variables a clique
 // shares with its parent, F the others in host axis order, R = prod card(F)) and on the belief tables alone.  The HOME of a query
@@ -25,14 +26,12 @@
 // the index, B = ceil(n / lanes), entry by entry (a mixed-radix counter, its digits in LDS, moves the table offset), and a fixed
 // tree of shuffles adds the lanes.  What is added in which order depends on n alone - not on the stored layout, of which nothing is
 // known here but the offsets jt_sample_at gives - so equal beliefs give bit-equal joints whatever the plan's flags.  A sum of
-// n >= 2 JT_JOINT_SEG terms (the root of a wide tree: 2^20 entries behind each of a handful of outputs) is cut into
-// min(4096, n / JT_JOINT_SEG) contiguous segments - of n alone again - each summed as above by a wave of its own;
+// n >= 2 JT_QUERY_SEG terms (the root of a wide tree: 2^20 entries behind each of a handful of outputs) is cut into
+// min(4096, n / JT_QUERY_SEG) contiguous segments - of n alone again - each summed as above by a wave of its own;
 // jt_joint_merge adds the segments' sums, lane l those of segments l, l + 64, ... in ascending order, then the same tree.
 // fail[0] counts the (clique, k) pairs that met a negative or NaN entry or whose sigma is not finite, fail[1] keeps the smallest
 // visit-order place among them; fail[2] is set where the top met such an entry or a sum of it is not finite (one more pair).
 
-#define JT_JOINT_KIDS 8          // active children of a clique whose records a workgroup stages in LDS (the others are read where they lie)
-#define JT_JOINT_SEG 1024        // terms of a segment
 #define JT_JOINT_CAP ((int64_t)64 << 20)      // bytes of the result, and of all sigma, M and segment sums of a call
 
 // the sum over the `lanes` lanes (a power of two) that share an entry, in every one of them: log2(lanes) shuffle steps
@@ -50,40 +49,24 @@ __global__ __launch_bounds__(256) void jt_joint_sigma(const JtJoint *__restrict_
     const JtJoint &rec = recs[blockIdx.y];
     const int tid = threadIdx.x, lane = tid & 63;
     const int nK = rec.nK, nF = rec.nFs;
-    for (int i = tid; i < nK * (int)(sizeof(JtSampleVar) / 4); i += 256) ((int32_t *)kv)[i] = ((const int32_t *)rec.v)[i];
-    for (int i = tid; i < nF * (int)(sizeof(JtSampleVar) / 4); i += 256) ((int32_t *)fv)[i] = ((const int32_t *)rec.f)[i];
+    jt_query_stage_vars(kv, rec.v, nK, tid);
+    jt_query_stage_vars(fv, rec.f, nF, tid);
     __syncthreads();
     const uint32_t R = rec.R, nk = rec.nk;
-    const uint32_t B = (R + 63u) >> 6;
     for (uint32_t k = blockIdx.x * 4u + (uint32_t)(tid >> 6); k < nk; k += gridDim.x * 4u) {      // (a whole wave)
         int64_t base = rec.bel_off;
         for (int j = 0; j < nK; ++j) base += jt_sample_at(kv[j], (int)((k / kv[j].radix) % (uint32_t)kv[j].card));
-        const uint32_t a = min((uint32_t)lane * B, R), e = min(a + B, R);
+        const auto [a, e, B] = jt_query_cut(0u, R, 64u, (uint32_t)lane);
         double sum = 0.0;
         bool bad = false;
         if (a < e) {
-            uint32_t off = 0;
-            for (int j = 0; j < nF; ++j) {
-                const int dg = (int)((a / fv[j].radix) % (uint32_t)fv[j].card);
-                digs[j][tid] = dg;
-                off += jt_sample_at(fv[j], dg);
-            }
+            uint32_t off = jt_query_walk_start(fv, nF, digs, tid, a);
             for (uint32_t q = a;;) {
                 const double w = (double)bel[base + off];
                 bad = bad || !(w >= 0.0);
                 sum += w;
                 if (++q == e) break;
-                for (int j = nF - 1; j >= 0; --j) {    // the next assignment in C order
-                    const JtSampleVar v = fv[j];
-                    const int dg = digs[j][tid];
-                    if (dg + 1 < v.card) {
-                        off += jt_sample_at(v, dg + 1) - jt_sample_at(v, dg);
-                        digs[j][tid] = dg + 1;
-                        break;
-                    }
-                    off -= jt_sample_at(v, dg);
-                    digs[j][tid] = 0;
-                }
+                off = jt_query_walk_next(fv, nF, digs, tid, off);
             }
         }
         sum = jt_joint_lanes_sum(sum, 64);
@@ -116,19 +99,18 @@ __global__ __launch_bounds__(256) void jt_joint_level(const JtJoint *__restrict_
     __shared__ int digs[JT_MAX_VARS][256];             // digit of v[j] in thread t's entry: a column per thread
     __shared__ JtSampleVar sv[JT_MAX_VARS];
     __shared__ JtJointX xs[JT_JOINT_MAXQ];
-    // the first JT_JOINT_KIDS active children: strides and place of the message, staged once; per thread and entry the part of the
+    // the first JT_QUERY_KIDS active children: strides and place of the message, staged once; per thread and entry the part of the
     // message index that (k, x) fix
-    __shared__ uint32_t kstride[JT_JOINT_KIDS][JT_MAX_VARS];
-    __shared__ uint32_t kxstride[JT_JOINT_KIDS][JT_JOINT_MAXQ];
-    __shared__ int64_t kmsg[JT_JOINT_KIDS];
-    __shared__ uint32_t kbase[JT_JOINT_KIDS][256];
+    __shared__ uint32_t kstride[JT_QUERY_KIDS][JT_MAX_VARS];
+    __shared__ uint32_t kxstride[JT_QUERY_KIDS][JT_JOINT_MAXQ];
+    __shared__ int64_t kmsg[JT_QUERY_KIDS];
+    __shared__ uint32_t kbase[JT_QUERY_KIDS][256];
     const JtJoint &rec = recs[blockIdx.y];
     const int tid = threadIdx.x;
     const int nK = rec.nK, nQ = rec.nQ, nF = rec.nF, nX = rec.nX, nfix = nK + nQ, nv = nfix + nF;
-    for (int i = tid; i < nv * (int)(sizeof(JtSampleVar) / 4); i += 256) ((int32_t *)sv)[i] = ((const int32_t *)rec.v)[i];
+    jt_query_stage_vars(sv, rec.v, nv, tid);
     for (int i = tid; i < nX * (int)(sizeof(JtJointX) / 4); i += 256) ((int32_t *)xs)[i] = ((const int32_t *)rec.x)[i];
-    const int n_kids = rec.child_end - rec.child_begin, n_staged = min(n_kids, JT_JOINT_KIDS);
-    for (int i = tid; i < n_staged * JT_MAX_VARS; i += 256) kstride[i / JT_MAX_VARS][i % JT_MAX_VARS] = kids[rec.child_begin + i / JT_MAX_VARS].stride[i % JT_MAX_VARS];
+    const int n_staged = jt_query_stage_kids(kstride, kids + rec.child_begin, rec.child_end - rec.child_begin, tid);
     for (int i = tid; i < n_staged * JT_JOINT_MAXQ; i += 256) kxstride[i / JT_JOINT_MAXQ][i % JT_JOINT_MAXQ] = kids[rec.child_begin + i / JT_JOINT_MAXQ].xstride[i % JT_JOINT_MAXQ];
     if (tid < n_staged) kmsg[tid] = kids[rec.child_begin + tid].msg_off;
     __syncthreads();
@@ -145,8 +127,7 @@ __global__ __launch_bounds__(256) void jt_joint_level(const JtJoint *__restrict_
         const uint32_t seg = live ? (uint32_t)(item % nseg) : 0u;
         const uint32_t k = (uint32_t)(entry / X), x = (uint32_t)(entry % X);
         const uint32_t lo = min(seg * seg_len, Rp), end = live ? min(lo + seg_len, Rp) : lo;
-        const uint32_t B = (end - lo + (uint32_t)lanes - 1u) / (uint32_t)lanes;
-        const uint32_t a = min(lo + (uint32_t)sub * B, end), e = min(a + B, end);
+        const auto [a, e, B] = jt_query_cut(lo, end, (uint32_t)lanes, (uint32_t)sub);
         double sum = 0.0;
         if (a < e) {
             int64_t base = rec.bel_off;
@@ -155,33 +136,22 @@ __global__ __launch_bounds__(256) void jt_joint_level(const JtJoint *__restrict_
                 if (xs[i].slot >= 0) digs[xs[i].slot][tid] = (int)((x / xs[i].radix) % (uint32_t)xs[i].card);
             for (int j = 0; j < nfix; ++j) base += jt_sample_at(sv[j], digs[j][tid]);
             for (int c = 0; c < n_staged; ++c) {
-                uint32_t at = 0;
-                for (int j = 0; j < nfix; ++j) at += (uint32_t)digs[j][tid] * kstride[c][j];
+                uint32_t at = jt_query_kid_at(0u, kstride[c], digs, tid, 0, nfix);
                 for (int i = 0; i < nX; ++i) at += ((x / xs[i].radix) % (uint32_t)xs[i].card) * kxstride[c][i];
                 kbase[c][tid] = at;
             }
-            uint32_t off = 0;
-            for (int j = 0; j < nF; ++j) {
-                const int dg = (int)((a / fv[j].radix) % (uint32_t)fv[j].card);
-                digs[nfix + j][tid] = dg;
-                off += jt_sample_at(fv[j], dg);
-            }
+            uint32_t off = jt_query_walk_start(fv, nF, digs + nfix, tid, a);
             for (uint32_t q = a;;) {
                 const T b = bel[base + off];
                 bad = bad || !(b >= (T)0);
                 double w = (double)b;
                 for (int c = 0; c < n_staged; ++c) {
-                    uint32_t at = kbase[c][tid];
-                    for (int j = nfix; j < nv; ++j) at += (uint32_t)digs[j][tid] * kstride[c][j];
+                    const uint32_t at = jt_query_kid_at(kbase[c][tid], kstride[c], digs, tid, nfix, nv);
                     w *= work[kmsg[c] + at];
                 }
                 for (int c = rec.child_begin + n_staged; c < rec.child_end; ++c) {      // (more children than are staged: ascending order still)
                     const JtJointChild &kid = kids[c];
-                    uint32_t at = 0;
-                    for (int j = 0; j < nv; ++j) {
-                        const uint32_t st = kid.stride[j];
-                        if (st) at += (uint32_t)digs[j][tid] * st;
-                    }
+                    uint32_t at = jt_query_kid_at(kid, digs, tid, nv);
                     for (int i = 0; i < nX; ++i) {
                         const uint32_t st = kid.xstride[i];
                         if (st) at += ((x / xs[i].radix) % (uint32_t)xs[i].card) * st;
@@ -190,17 +160,7 @@ __global__ __launch_bounds__(256) void jt_joint_level(const JtJoint *__restrict_
                 }
                 sum += w;
                 if (++q == e) break;
-                for (int j = nF - 1; j >= 0; --j) {    // the next assignment in C order
-                    const JtSampleVar v = fv[j];
-                    const int dg = digs[nfix + j][tid];
-                    if (dg + 1 < v.card) {
-                        off += jt_sample_at(v, dg + 1) - jt_sample_at(v, dg);
-                        digs[nfix + j][tid] = dg + 1;
-                        break;
-                    }
-                    off -= jt_sample_at(v, dg);
-                    digs[nfix + j][tid] = 0;
-                }
+                off = jt_query_walk_next(fv, nF, digs + nfix, tid, off);
             }
         }
         sum = jt_joint_lanes_sum(sum, lanes);
@@ -294,23 +254,11 @@ static int joint_records(const HostPlan &hp, int n_query, const int32_t *q, Join
     const int64_t report = at;
     for (size_t i = 0; i < act.size(); ++i) {
         const SampleClique &sc = hp.sample[act[i]];
-        const JtPackDesc &d = hp.pack[sc.clique];
         JtJoint &r = jq.recs[i];
         memset(&r, 0, sizeof r);
-        r.bel_off = d.dev_off;
+        r.bel_off = hp.pack[sc.clique].dev_off;
         r.ord = act[i];
         r.top = i == 0;
-        auto var_of = [&](int v, JtSampleVar &sv) {
-            int i_host = 0;                                  // the variable's place in the clique's host axis order: the index into the pack record
-            while (hp.node_vars[sc.clique][i_host] != v) ++i_host;
-            sv.col = v;
-            sv.card = d.card[i_host];
-            sv.stride = d.dstride[i_host];
-            sv.stride2 = 0;
-            sv.lb = 31;
-            if (d.row_elems > 0 && i_host == d.split_var) sv.lb = d.split_lb, sv.stride2 = d.split_ds2;
-            sv.radix = 1;
-        };
         std::vector<int> own;                                // positions in the query of Q_c
         for (int p : carried[i])
             if (home[p] == act[i]) own.push_back(p);
@@ -325,7 +273,7 @@ static int joint_records(const HostPlan &hp, int n_query, const int32_t *q, Join
         r.nF = (int32_t)vs.size() - r.nK - r.nQ;
         uint32_t radix_k = 1, radix_f = 1;
         for (int j = (int)vs.size() - 1; j >= 0; --j) {
-            var_of(vs[j], r.v[j]);
+            r.v[j] = jt_query_var(hp, sc.clique, vs[j]);
             if (j >= r.nK + r.nQ) r.v[j].radix = radix_f, radix_f *= (uint32_t)r.v[j].card;
             else if (j < r.nK) r.v[j].radix = radix_k, radix_k *= (uint32_t)r.v[j].card;
         }
@@ -333,7 +281,7 @@ static int joint_records(const HostPlan &hp, int n_query, const int32_t *q, Join
         r.Rp = radix_f;
         r.nFs = (int32_t)sc.F.size();
         uint32_t radix = 1;
-        for (int j = r.nFs - 1; j >= 0; --j) var_of(sc.F[j], r.f[j]), r.f[j].radix = radix, radix *= (uint32_t)r.f[j].card;
+        for (int j = r.nFs - 1; j >= 0; --j) r.f[j] = jt_query_var(hp, sc.clique, sc.F[j]), r.f[j].radix = radix, radix *= (uint32_t)r.f[j].card;
         r.R = radix;
         r.lanes = 1;
         while (r.lanes < 64 && (uint32_t)r.lanes < r.Rp) r.lanes <<= 1;
@@ -351,7 +299,7 @@ static int joint_records(const HostPlan &hp, int n_query, const int32_t *q, Join
             X *= jx.card;
         }
         r.X = (uint32_t)X;                                   // (at most the result's entries)
-        r.nseg = r.Rp >= 2u * JT_JOINT_SEG ? std::min<uint32_t>(4096u, r.Rp / JT_JOINT_SEG) : 1u;
+        r.nseg = jt_query_nseg(r.Rp, JT_QUERY_SEG);
         const int64_t msg = (int64_t)r.nk * X;
         if (!r.top) {
             r.sig_off = at;
@@ -458,17 +406,14 @@ int jtp_joint(jtp_plan *pl, int32_t batch, int32_t n_query, const int32_t *var_i
     const unsigned long long fail0[4] = {0ull, ~0ull, 0ull, 0ull};
     HIP_TRY(hipMemcpyAsync(dfail, fail0, sizeof fail0, hipMemcpyHostToDevice, s));
     const size_t n_rec = jq.recs.size();
-    for (size_t y0 = 1; y0 < n_rec; y0 += 65535) {           // (sigma does not depend on the depth: every clique but the top at once)
-        const size_t ny = std::min<size_t>(65535, n_rec - y0);
-        const dim3 grid((unsigned)std::min<int64_t>(((int64_t)jq.max_nk + 3) / 4, std::max<int64_t>(64, 32768 / (int64_t)ny)), (unsigned)ny);
-        if (hp.dtype == JTP_F32) hipLaunchKernelGGL(jt_joint_sigma<float>, grid, dim3(256), 0, s, recs + y0, (const float *)b.bel, work, dfail);
-        else hipLaunchKernelGGL(jt_joint_sigma<double>, grid, dim3(256), 0, s, recs + y0, (const double *)b.bel, work, dfail);
-    }
+    jt_query_slices(n_rec - 1, [&](size_t y0, size_t ny) {    // (sigma does not depend on the depth: every clique but the top - record 0, always there - at once)
+        const dim3 grid(jt_query_grid_x(((int64_t)jq.max_nk + 3) / 4, ny), (unsigned)ny);
+        JT_QUERY_LAUNCH(hp.dtype, jt_joint_sigma, grid, s, recs + 1 + y0, (const T *)b.bel, work, dfail);
+    });
     for (size_t d = jq.depth_range.size(); d-- > 0;) {
         const int y0 = jq.depth_range[d].first, ny = jq.depth_range[d].second - y0;      // (at most one clique per query variable)
-        const dim3 grid((unsigned)std::min<int64_t>(jq.depth_items[d], std::max<int64_t>(64, 32768 / (int64_t)ny)), (unsigned)ny);
-        if (hp.dtype == JTP_F32) hipLaunchKernelGGL(jt_joint_level<float>, grid, dim3(256), 0, s, recs + y0, kids, (const float *)b.bel, work, dfail);
-        else hipLaunchKernelGGL(jt_joint_level<double>, grid, dim3(256), 0, s, recs + y0, kids, (const double *)b.bel, work, dfail);
+        const dim3 grid(jt_query_grid_x(jq.depth_items[d], (size_t)ny), (unsigned)ny);
+        JT_QUERY_LAUNCH(hp.dtype, jt_joint_level, grid, s, recs + y0, kids, (const T *)b.bel, work, dfail);
         if (jq.depth_merge[d]) {
             const dim3 mgrid((unsigned)std::min<int64_t>((jq.depth_merge[d] + 3) / 4, 1024), (unsigned)ny);
             hipLaunchKernelGGL(jt_joint_merge, mgrid, dim3(256), 0, s, recs + y0, work, dfail);

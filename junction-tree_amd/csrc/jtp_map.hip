@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "jtp_engine.h"
+#include "jtp_query.h"
 
 // jtp_map works on the sampling schedule (HostPlan::sample: the caller's tree by depth, then clique number; K the variables a clique
 // shares with its parent, F the others in host axis order, R = prod card(F)) and on the potentials alone - no propagate is needed or
@@ -22,9 +23,6 @@
 // set reads arg_c[k] at the digits the cliques above wrote and writes the digits of F_c.
 // A set fails where an entry that agrees with its evidence is negative or NaN, or where a clique's maximum is zero or not finite
 // (the root's then is): its states are -1.
-
-#define JT_MAP_KIDS 8          // children of a clique whose records a workgroup stages in LDS (the others are read where they lie)
-#define JT_MAP_SEG 1024        // entries of a segment (jtp_debug_set "map_seg" overrides it: tools/map_time.py)
 
 // ilogb of the finite double >= 0 with this bit pattern (0 for 0.0)
 __host__ __device__ static inline int jt_map_exp(unsigned long long bits) {
@@ -88,20 +86,19 @@ __global__ __launch_bounds__(256) void jt_map_collect_level(const JtMap *__restr
     __shared__ int digs[JT_MAX_VARS][256];             // digit j of thread t's counter: a column per thread (K digits: the wave's, in every column)
     __shared__ JtSampleVar sv[JT_MAX_VARS];
     __shared__ int obs[4][JT_MAX_VARS];                // per wave: the observed state of v[j] in the wave's set, -1: none
-    // the first JT_MAP_KIDS children: strides, place of the raw table and record, staged once; per wave and item the part of the
+    // the first JT_QUERY_KIDS children: strides, place of the raw table and record, staged once; per wave and item the part of the
     // index the K digits fix and the exponent of the child's maximum (read from global memory per entry, each of these is a
     // dependent scalar load: 12 000 cycles an entry on the width-20 tree)
-    __shared__ uint32_t kstride[JT_MAP_KIDS][JT_MAX_VARS];
-    __shared__ int64_t kraw[JT_MAP_KIDS];
-    __shared__ int kord[JT_MAP_KIDS];
-    __shared__ uint32_t kbase[4][JT_MAP_KIDS];
-    __shared__ int kexp[4][JT_MAP_KIDS];
+    __shared__ uint32_t kstride[JT_QUERY_KIDS][JT_MAX_VARS];
+    __shared__ int64_t kraw[JT_QUERY_KIDS];
+    __shared__ int kord[JT_QUERY_KIDS];
+    __shared__ uint32_t kbase[4][JT_QUERY_KIDS];
+    __shared__ int kexp[4][JT_QUERY_KIDS];
     const JtMap &rec = recs[blockIdx.y];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int nK = rec.nK, nF = rec.nF, nv = nK + nF;
-    for (int i = tid; i < nv * (int)(sizeof(JtSampleVar) / 4); i += 256) ((int32_t *)sv)[i] = ((const int32_t *)rec.v)[i];
-    const int n_kids = rec.child_end - rec.child_begin, n_staged = min(n_kids, JT_MAP_KIDS);
-    for (int i = tid; i < n_staged * JT_MAX_VARS; i += 256) kstride[i / JT_MAX_VARS][i % JT_MAX_VARS] = kids[rec.child_begin + i / JT_MAX_VARS].stride[i % JT_MAX_VARS];
+    jt_query_stage_vars(sv, rec.v, nv, tid);
+    const int n_staged = jt_query_stage_kids(kstride, kids + rec.child_begin, rec.child_end - rec.child_begin, tid);
     if (tid < n_staged) kraw[tid] = kids[rec.child_begin + tid].raw_off, kord[tid] = kids[rec.child_begin + tid].ord;
     __syncthreads();
     const JtSampleVar *fv = sv + nK;
@@ -128,19 +125,17 @@ __global__ __launch_bounds__(256) void jt_map_collect_level(const JtMap *__restr
         const double *raw_set = wk.raw + (int64_t)set * entries;
         const unsigned long long *top_set = wk.top + (int64_t)set * n_rec;
         if (lane < n_staged) {                             // (the K digits are in every lane's column)
-            uint32_t at = 0;
-            for (int j = 0; j < nK; ++j) at += (uint32_t)digs[j][tid] * kstride[lane][j];
-            kbase[wave][lane] = at;
+            kbase[wave][lane] = jt_query_kid_at(0u, kstride[lane], digs, tid, 0, nK);
             kexp[wave][lane] = jt_map_exp(top_set[kord[lane]]);
         }
         __builtin_amdgcn_wave_barrier();
         const uint32_t lo = min(seg * seg_len, R), end = min(lo + seg_len, R);
-        const uint32_t B = (end - lo + 63u) >> 6;
-        const uint32_t a = min(lo + (uint32_t)lane * B, end), e = min(a + B, end);
+        const auto [a, e, B] = jt_query_cut(lo, end, 64u, (uint32_t)lane);
         double best = -1.0;                                // (nothing looked at yet: every w >= 0 beats it)
         uint32_t best_r = 0xffffffffu;
         bool bad = false;
         if (!dead && a < e) {
+            // (the walk of jtp_query.h, written out: the count of contradictions is kept with the digits - see the note there)
             uint32_t off = 0;
             int contra = 0;                                // digits of F that contradict the evidence
             for (int j = 0; j < nF; ++j) {
@@ -155,18 +150,12 @@ __global__ __launch_bounds__(256) void jt_map_collect_level(const JtMap *__restr
                     bad = bad || !(x >= (T)0);
                     double w = (double)x;
                     for (int c = 0; c < n_staged; ++c) {
-                        uint32_t at = kbase[wave][c];
-                        for (int j = nK; j < nv; ++j) at += (uint32_t)digs[j][tid] * kstride[c][j];
+                        const uint32_t at = jt_query_kid_at(kbase[wave][c], kstride[c], digs, tid, nK, nv);
                         w *= ldexp(raw_set[kraw[c] + at], -kexp[wave][c]);
                     }
                     for (int c = rec.child_begin + n_staged; c < rec.child_end; ++c) {      // (more children than are staged: ascending order still)
                         const JtMapChild &kid = kids[c];
-                        uint32_t at = 0;
-                        for (int j = 0; j < nv; ++j) {
-                            const uint32_t st = kid.stride[j];
-                            if (st) at += (uint32_t)digs[j][tid] * st;
-                        }
-                        w *= ldexp(raw_set[kid.raw_off + at], -jt_map_exp(top_set[kid.ord]));
+                        w *= ldexp(raw_set[kid.raw_off + jt_query_kid_at(kid, digs, tid, nv)], -jt_map_exp(top_set[kid.ord]));
                     }
                     if (w > best) best = w, best_r = q;    // (ascending r: the first of equals stays; a NaN is never taken)
                 }
@@ -257,33 +246,23 @@ static void map_records(const HostPlan &hp, uint32_t seg, std::vector<JtMap> &re
     mm.entries = mm.parts = 0;
     for (size_t i = 0; i < n; ++i) {
         const SampleClique &sc = hp.sample[i];
-        const JtPackDesc &d = hp.pack[sc.clique];
         JtMap &r = recs[i];
         memset(&r, 0, sizeof r);
-        r.psi_off = d.dev_off;
+        r.psi_off = hp.pack[sc.clique].dev_off;
         r.nK = (int32_t)sc.K.size();
         r.nF = (int32_t)sc.F.size();
         r.R = (uint32_t)sc.R;
         r.ord = (int32_t)i;
         uint32_t radix_k = 1, radix_f = 1;
         for (int j = r.nK + r.nF - 1; j >= 0; --j) {
-            const int v = j < r.nK ? sc.K[j] : sc.F[j - r.nK];
-            int i_host = 0;                              // the variable's place in the clique's host axis order: the index into the pack record
-            while (hp.node_vars[sc.clique][i_host] != v) ++i_host;
-            JtSampleVar &sv = r.v[j];
-            sv.col = v;
-            sv.card = d.card[i_host];
-            sv.stride = d.dstride[i_host];
-            sv.stride2 = 0;
-            sv.lb = 31;
-            if (d.row_elems > 0 && i_host == d.split_var) sv.lb = d.split_lb, sv.stride2 = d.split_ds2;
+            JtSampleVar &sv = r.v[j] = jt_query_var(hp, sc.clique, j < r.nK ? sc.K[j] : sc.F[j - r.nK]);
             if (j >= r.nK) sv.radix = radix_f, radix_f *= (uint32_t)sv.card;
             else sv.radix = radix_k, radix_k *= (uint32_t)sv.card;
         }
         r.nk = radix_k;
         // (a wave per k walks R entries, 64 lanes wide: from two segments' worth on, segments of `seg` entries or more - the root of a
         //  wide tree has one k)
-        r.nseg = r.R >= 2u * seg ? std::min<uint32_t>(4096u, r.R / seg) : 1u;
+        r.nseg = jt_query_nseg(r.R, seg);
         r.raw_off = mm.entries;
         mm.entries += r.nk;
         r.part_off = mm.parts;
@@ -349,7 +328,7 @@ int jtp_map(jtp_plan *pl, int32_t batch_begin, int32_t batch_end, int32_t *state
         std::vector<JtMap> recs;
         std::vector<JtMapChild> kids;
         std::vector<int32_t> depth_begin;
-        map_records(hp, (uint32_t)std::min<int64_t>(pl->map_seg > 0 ? pl->map_seg : JT_MAP_SEG, 1 << 30), recs, kids, depth_begin, fresh);
+        map_records(hp, (uint32_t)std::min<int64_t>(pl->map_seg > 0 ? pl->map_seg : JT_QUERY_SEG, 1 << 30), recs, kids, depth_begin, fresh);
         HIP_TRY(fresh.recs.upload(recs, 1));
         HIP_TRY(fresh.kids.upload(kids, 1));
         HIP_TRY(fresh.depth_begin.upload(depth_begin, 1));
@@ -387,20 +366,16 @@ int jtp_map(jtp_plan *pl, int32_t batch_begin, int32_t batch_end, int32_t *state
         if (n_vars) HIP_TRY(hipMemsetAsync(wk.states, 0, cnt * n_vars * sizeof(int32_t), s));      // (a variable of no clique stays 0)
         for (int d = n_depths - 1; d >= 0; --d) {
             const std::vector<int> &level = hp.sample_depths[d];
-            for (size_t y0 = 0; y0 < level.size(); y0 += 65535) {
-                const size_t ny = std::min<size_t>(65535, level.size() - y0);
+            jt_query_slices(level.size(), [&](size_t y0, size_t ny) {
                 const int64_t waves = (int64_t)cnt * mm.depth_items[d];
-                const dim3 grid((unsigned)std::min<int64_t>((waves + 3) / 4, std::max<int64_t>(64, 32768 / (int64_t)ny)), (unsigned)ny);
+                const dim3 grid(jt_query_grid_x((waves + 3) / 4, ny), (unsigned)ny);
                 const JtMap *recs = mm.recs.get() + level[0] + y0;
-                if (hp.dtype == JTP_F32)
-                    hipLaunchKernelGGL(jt_map_collect_level<float>, grid, dim3(256), 0, s, recs, mm.kids.get(), wk, (int)n_vars, (int)n_rec, (int)cnt, (int64_t)entries, (int64_t)parts);
-                else
-                    hipLaunchKernelGGL(jt_map_collect_level<double>, grid, dim3(256), 0, s, recs, mm.kids.get(), wk, (int)n_vars, (int)n_rec, (int)cnt, (int64_t)entries, (int64_t)parts);
+                JT_QUERY_LAUNCH(hp.dtype, jt_map_collect_level, grid, s, recs, mm.kids.get(), wk, (int)n_vars, (int)n_rec, (int)cnt, (int64_t)entries, (int64_t)parts);
                 if (mm.depth_merge[d]) {
-                    const dim3 mgrid((unsigned)std::min<int64_t>(((int64_t)cnt * mm.depth_items[d] + 3) / 4, 1024), (unsigned)ny);
+                    const dim3 mgrid((unsigned)std::min<int64_t>((waves + 3) / 4, 1024), (unsigned)ny);
                     hipLaunchKernelGGL(jt_map_merge, mgrid, dim3(256), 0, s, recs, wk, (int)n_rec, (int)cnt, (int64_t)entries, (int64_t)parts);
                 }
-            }
+            });
         }
         hipLaunchKernelGGL(jt_map_decode, dim3((unsigned)cnt), dim3(256), 0, s, mm.recs.get(), mm.depth_begin.get(), n_depths, wk, (int)n_vars, (int)n_rec, (int64_t)entries);
         HIP_TRY(hipGetLastError());

@@ -105,27 +105,6 @@ struct JtRescale {
     int32_t pad;
 };
 
-// jtp_sample: one record per clique of the sampling schedule (SampleClique), read by the kernel jt_sample_level as it stands.  The
-// conditioning variables come first, then the drawn ones, both in host axis order.  A digit's place in the belief table is linear
-// in the digit - the `back` sum of jt_dev_to_host - in two parts for the variable across the thread part's top bit of a compact
-// row (JtPackDesc::split_var): (digit mod 2^lb) * stride + (digit >> lb) * stride2; every other variable has lb = 31, stride2 = 0.
-struct JtSampleVar {                 // 24 bytes
-    int32_t col;                     // column of the state row (variable id)
-    int32_t card;
-    uint32_t stride, stride2;        // device element strides
-    int32_t lb;
-    uint32_t radix;                  // drawn variables: product of the cardinalities of the drawn variables behind this one (C order)
-};
-struct JtSample {
-    int64_t bel_off;                 // element offset of the clique's table in the belief arena
-    int32_t nK, nF;
-    uint32_t R;                      // entries of one slice: product of the cardinalities of the drawn variables
-    int32_t clique;                  // C-ABI clique number: the random stream's key
-    int32_t ord;                     // place in the visit order (the failure report keeps the smallest)
-    int32_t pad;
-    JtSampleVar v[JT_MAX_VARS];      // [0, nK): conditioning; [nK, nK + nF): drawn
-};
-
 // Dataflow schedule: consecutive launches of one phase run as ONE launch whose workgroups take
 // their place in the block list from a ticket counter and wait on message completion counters.
 struct Segment {

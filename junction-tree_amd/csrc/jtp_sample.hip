@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "jtp_engine.h"
+#include "jtp_query.h"
 
 // jtp_sample: one launch per depth of the caller's tree (HostPlan::sample_depths), a wave64 per (clique, sample), four per
 // workgroup; blockIdx.y = the clique's record, blockIdx.x * 4 + wave = the sample of the chunk.  The wave reads the sample's
@@ -31,7 +32,7 @@ __global__ __launch_bounds__(256) void jt_sample_level(const JtSample *__restric
     const JtSample &rec = recs[blockIdx.y];
     const int tid = threadIdx.x, lane = tid & 63;
     const int nK = rec.nK, nF = rec.nF;
-    for (int i = tid; i < (nK + nF) * (int)(sizeof(JtSampleVar) / 4); i += 256) ((int32_t *)sv)[i] = ((const int32_t *)rec.v)[i];
+    jt_query_stage_vars(sv, rec.v, nK + nF, tid);
     __syncthreads();
     const int local = blockIdx.x * 4 + (tid >> 6);
     if (local >= n_chunk) return;                      // (a whole wave)
@@ -50,33 +51,18 @@ __global__ __launch_bounds__(256) void jt_sample_level(const JtSample *__restric
     double target = 0.0;
     bool whole = true;
     while (!dead) {
-        const uint32_t B = (len + 63u) >> 6, end = lo + len;
-        const uint32_t a = min(lo + (uint32_t)lane * B, end), e = min(a + B, end);
+        const uint32_t end = lo + len;
+        const auto [a, e, B] = jt_query_cut(lo, end, 64u, (uint32_t)lane);
         double sum = 0.0;
         bool bad = false;
         if (a < e) {
-            uint32_t off = 0;
-            for (int k = 0; k < nF; ++k) {
-                const int dg = (int)((a / fv[k].radix) % (uint32_t)fv[k].card);
-                digs[k][tid] = dg;
-                off += jt_sample_at(fv[k], dg);
-            }
+            uint32_t off = jt_query_walk_start(fv, nF, digs, tid, a);
             for (uint32_t q = a;;) {
                 const double w = (double)bel[base + off];
                 bad = bad || !(w >= 0.0);
                 sum += w;
                 if (++q == e) break;
-                for (int k = nF - 1; k >= 0; --k) {    // the next assignment in C order
-                    const JtSampleVar v = fv[k];
-                    const int dg = digs[k][tid];
-                    if (dg + 1 < v.card) {
-                        off += jt_sample_at(v, dg + 1) - jt_sample_at(v, dg);
-                        digs[k][tid] = dg + 1;
-                        break;
-                    }
-                    off -= jt_sample_at(v, dg);
-                    digs[k][tid] = 0;
-                }
+                off = jt_query_walk_next(fv, nF, digs, tid, off);
             }
         }
         double inc = sum;
@@ -139,14 +125,13 @@ int jtp_sample(jtp_plan *pl, int32_t batch, int32_t n_samples, uint64_t seed, in
     //  allocates is there - a call that fails leaves the plan as it found it)
     DeviceBuf<JtSample> recs_dev(&pl->mem);
     DeviceBuf<unsigned long long> fail_dev(&pl->mem);
-    if (!pl->d_sample) {
+    if (!pl->sample.recs) {
         std::vector<JtSample> recs(hp.sample.size());
         for (size_t i = 0; i < recs.size(); ++i) {
             const SampleClique &sc = hp.sample[i];
-            const JtPackDesc &d = hp.pack[sc.clique];
             JtSample &r = recs[i];
             memset(&r, 0, sizeof r);
-            r.bel_off = d.dev_off;
+            r.bel_off = hp.pack[sc.clique].dev_off;
             r.nK = (int32_t)sc.K.size();
             r.nF = (int32_t)sc.F.size();
             r.R = (uint32_t)sc.R;
@@ -154,44 +139,31 @@ int jtp_sample(jtp_plan *pl, int32_t batch, int32_t n_samples, uint64_t seed, in
             r.ord = (int32_t)i;
             uint32_t radix = 1;
             for (int j = r.nK + r.nF - 1; j >= 0; --j) {
-                const int v = j < r.nK ? sc.K[j] : sc.F[j - r.nK];
-                int i_host = 0;                          // the variable's place in the clique's host axis order: the index into the pack record
-                while (hp.node_vars[sc.clique][i_host] != v) ++i_host;
-                JtSampleVar &sv = r.v[j];
-                sv.col = v;
-                sv.card = d.card[i_host];
-                sv.stride = d.dstride[i_host];
-                sv.stride2 = 0;
-                sv.lb = 31;
-                if (d.row_elems > 0 && i_host == d.split_var) sv.lb = d.split_lb, sv.stride2 = d.split_ds2;
-                sv.radix = 1;
+                JtSampleVar &sv = r.v[j] = jt_query_var(hp, sc.clique, j < r.nK ? sc.K[j] : sc.F[j - r.nK]);
                 if (j >= r.nK) sv.radix = radix, radix *= (uint32_t)sv.card;
             }
         }
         HIP_TRY(recs_dev.upload(recs, 1));
     }
-    if (!pl->d_sample_fail) HIP_TRY(fail_dev.alloc(2));
+    if (!pl->sample.fail) HIP_TRY(fail_dev.alloc(2));
     // samples go in chunks through one buffer of state rows (at most 64 MiB of them, 256 .. 65536 rows): the grid stays within
     // limits whatever n_samples is, and there is one copy back per chunk
     const size_t chunk = std::min<size_t>((size_t)n_samples, std::max<size_t>(256, std::min<size_t>(65536, ((size_t)16 << 20) / (size_t)n_vars)));
-    HIP_TRY(pl->sample_states.reserve(chunk * (size_t)n_vars));
-    if (recs_dev) pl->d_sample = std::move(recs_dev);
-    if (fail_dev) pl->d_sample_fail = std::move(fail_dev);
-    int32_t *rows = pl->sample_states.get();
-    unsigned long long *dfail = pl->d_sample_fail.get();
+    HIP_TRY(pl->sample.states.reserve(chunk * (size_t)n_vars));
+    if (recs_dev) pl->sample.recs = std::move(recs_dev);
+    if (fail_dev) pl->sample.fail = std::move(fail_dev);
+    int32_t *rows = pl->sample.states.get();
+    unsigned long long *dfail = pl->sample.fail.get();
     HIP_TRY(hipMemsetAsync(dfail, 0, sizeof(unsigned long long), s));
     HIP_TRY(hipMemsetAsync(dfail + 1, 0xff, sizeof(unsigned long long), s));
     for (size_t at = 0; at < (size_t)n_samples; at += chunk) {
         const size_t cnt = std::min(chunk, (size_t)n_samples - at);
         HIP_TRY(hipMemsetAsync(rows, 0xff, cnt * (size_t)n_vars * sizeof(int32_t), s));      // (-1: nothing drawn yet)
         for (const std::vector<int> &level : hp.sample_depths)
-            for (size_t y0 = 0; y0 < level.size(); y0 += 65535) {                                         // (records of a depth are consecutive)
-                const dim3 grid((unsigned)((cnt + 3) / 4), (unsigned)std::min<size_t>(65535, level.size() - y0));
-                if (hp.dtype == JTP_F32)
-                    hipLaunchKernelGGL(jt_sample_level<float>, grid, dim3(256), 0, s, pl->d_sample.get() + level[0] + y0, (const float *)b.bel, rows, n_vars, (int)cnt, (uint64_t)at, seed, dfail);
-                else
-                    hipLaunchKernelGGL(jt_sample_level<double>, grid, dim3(256), 0, s, pl->d_sample.get() + level[0] + y0, (const double *)b.bel, rows, n_vars, (int)cnt, (uint64_t)at, seed, dfail);
-            }
+            jt_query_slices(level.size(), [&](size_t y0, size_t ny) {                                     // (records of a depth are consecutive)
+                const dim3 grid((unsigned)((cnt + 3) / 4), (unsigned)ny);
+                JT_QUERY_LAUNCH(hp.dtype, jt_sample_level, grid, s, pl->sample.recs.get() + level[0] + y0, (const T *)b.bel, rows, n_vars, (int)cnt, (uint64_t)at, seed, dfail);
+            });
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpyAsync(states + at * (size_t)n_vars, rows, cnt * (size_t)n_vars * sizeof(int32_t), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));                // (the buffer is the next chunk's)

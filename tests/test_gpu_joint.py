@@ -40,7 +40,7 @@ _cases = {}
 
 def case(name):
     if name not in _cases:
-        _cases[name] = mixed_case() if name == "random16_mixed" else star_case(5) if name == "star5" else case_of(name)
+        _cases[name] = mixed_case() if name == "random16_mixed" else star_case(int(name[4:])) if name.startswith("star") else case_of(name)
     return _cases[name]
 
 
@@ -89,6 +89,9 @@ def queries(name):
     if name == "star5":
         kids = sorted(c for c in parent if parent[c] == sched[0][0])
         return {"three_children_and_the_root": [F[kids[3]][0], F[kids[0]][0], F[sched[0][0]][0], F[kids[4]][0]]}
+    if name == "star12":                                  # the hub is the top; eight of its active children are staged, two read in place
+        kids = sorted(c for c in parent if parent[c] == sched[0][0])
+        return {"ten_children": [F[kids[i]][0] for i in (9, 0, 11, 3, 7, 1, 10, 4, 6, 2)]}
     # the random trees: the two deepest cliques that draw something and do not lie on one path, and the root
     def path(c):
         out = [c]
@@ -121,7 +124,7 @@ def check_parity(plan, cs, query, what):
 
 # ---------------------------------------------------------------------------------------------- 1. parity with the restatement
 
-NAMES = ["wide7", "chain6", "star5", "random16_card3", "random16_mixed"]
+NAMES = ["wide7", "chain6", "star5", "star12", "random16_card3", "random16_mixed"]
 RUNS = [(n, d, {}) for n in NAMES for d in ("f64", "f32")] + [("random16_card3", "f64", dict(no_compact=True)), ("random16_mixed", "f32", dict(no_compact=True)),
                                                               ("wide7", "f32", dict(no_compact=True)), ("chain6", "f64", dict(no_compact=True))]
 
@@ -160,6 +163,7 @@ def test_the_queries_cover_what_they_are_there_for():
             seen.update("R' cut into segments" for _, r, rp, m in report if rp >= 2048)
             seen.update("two active children" for _, r, rp, m in report if m >= 2)
             seen.update("three active children" for _, r, rp, m in report if m >= 3)
+            seen.update("more active children than are staged" for _, r, rp, m in report if m >= 9)
             if len(set(home.values())) < len(query):
                 seen.add("a clique home to two query variables")
             if len(report) == 1:
@@ -176,6 +180,7 @@ def test_the_queries_cover_what_they_are_there_for():
             if list(query) != tree_order:
                 seen.add("an order that is not the tree's")
     assert seen >= {"top is the root", "top is not the root", "R' > 64", "R' = 1", "R' cut into segments", "two active children", "three active children",
+                    "more active children than are staged",
                     "a clique home to two query variables", "one clique", "carried across three cliques", "an order that is not the tree's"}, seen
     # ... and among the active cliques of the cardinality cases are tables stored as mixed-radix rows, one with a variable across
     # the thread part's top bit
