@@ -6,6 +6,7 @@ The shared library lands in junctiontree_amd/lib/ (git-ignored; it travels to th
 with the gpurun snapshot).  hipcc cross-compiles without a GPU.
 """
 import os
+import re
 import subprocess
 import sys
 
@@ -20,23 +21,40 @@ ENGINE = ["jtp_engine.hip", "jtp_upload.hip", "jtp_propagate.hip", "jtp_readout.
 # (the planner's units, pure host C++: csrc/jtp_plan_build.h has the map)
 PLANNER = ["jtp_plan.cpp", "jtp_plan_layout.cpp", "jtp_plan_loops.cpp", "jtp_plan_tasks.cpp", "jtp_plan_schedule.cpp", "jtp_plan_json.cpp"]
 SOURCES = PLANNER + ENGINE + INST                # (compiled in parallel, one object each, then linked)
-HEADERS = ["jtp_internal.h", "jtp_plan.h", "jtp_kernels.hip.h", "jtp_device.h", "jtp_engine.h", "jtp_query.h", os.path.join("..", "..", "include", "jtprop.h")]
-PLANNER_HEADERS = ["jtp_plan.h", "jtp_plan_build.h", "jtp_internal.h", os.path.join("..", "..", "include", "jtprop.h")]
-DEPS = SOURCES + HEADERS + ["jtp_plan_build.h"]
+INCLUDE = re.compile(rb'^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', re.M)
 
 
 ID_FILE = os.path.join(LIBDIR, "BUILD_ID")
 
 
-def source_id():
-    """Digest of everything libjtprop.so is compiled from: identifies the CODE a profile was measured on
-    (jtp_version() ends in it; tools/collect_profiles.sh stamps it into the files under profiles/)."""
+def unit_deps(src, csrc=None):
+    """The files a unit is compiled from besides itself: what its quoted #include lines reach, followed from file to file (the
+    project's own headers, in csrc/ and include/jtprop.h; <...> includes are the toolchain's).  Names are relative to csrc/, sorted."""
+    csrc = csrc or CSRC
+    seen, todo = set(), [src]
+    while todo:
+        with open(os.path.join(csrc, todo.pop()), "rb") as fh:
+            for inc in map(bytes.decode, INCLUDE.findall(fh.read())):
+                if inc not in seen:
+                    seen.add(inc)
+                    todo.append(inc)
+    return sorted(seen)
+
+
+def digest(names, csrc=None):
+    """sha256 over the named files (relative to csrc/), names included"""
     import hashlib
     h = hashlib.sha256()
-    for d in sorted(DEPS):
-        with open(os.path.join(CSRC, d), "rb") as fh:
+    for d in names:
+        with open(os.path.join(csrc or CSRC, d), "rb") as fh:
             h.update(d.encode() + b"\0" + fh.read())
-    return h.hexdigest()[:12]
+    return h
+
+
+def source_id(csrc=None):
+    """Digest of everything libjtprop.so is compiled from: identifies the CODE a profile was measured on
+    (jtp_version() ends in it; tools/collect_profiles.sh stamps it into the files under profiles/)."""
+    return digest(sorted(set(SOURCES).union(*(unit_deps(src, csrc) for src in SOURCES))), csrc).hexdigest()[:12]
 
 
 def built_id():
@@ -72,14 +90,12 @@ def build(force=False, verbose=True, extra=(), out=None, jobs=None):
     flags = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-unused-variable",
              '-DJTP_SOURCE_ID="%s"' % sid] + list(extra)
     objdir = tempfile.mkdtemp(prefix="jtprop_build_")
-    # objects of translation units whose sources did not change are taken from a cache beside the library (git-ignored):
-    # a change to one planner unit recompiles that unit alone; one to the planner's face (jtp_plan.h) the planner and the engine's units,
-    # never the kernel instantiation units
+    # objects of translation units whose sources did not change are taken from a cache beside the library (git-ignored).  A unit's
+    # sources are its own text and what it includes (unit_deps): a change to one planner unit recompiles that unit alone; one to the
+    # planner's face (jtp_plan.h) the planner and the engine's units, never the kernel instantiation units; one to a kernel unit
+    # (jtp_k_*.h) the instantiation units of the families that include it, never the engine
     cache = os.path.join(LIBDIR, "objcache")
     os.makedirs(cache, exist_ok=True)
-    import hashlib
-    headers = dict((src, PLANNER_HEADERS) for src in PLANNER)
-    headers.update((src, HEADERS) for src in ENGINE)       # (every engine unit: all of them, the simplest rule that is right)
     try:                       # (the compiler is part of what an object is made of: a toolchain upgrade must not link old objects)
         toolchain = subprocess.check_output([hipcc, "--version"], stderr=subprocess.STDOUT)
     except (OSError, subprocess.CalledProcessError):
@@ -87,11 +103,8 @@ def build(force=False, verbose=True, extra=(), out=None, jobs=None):
     try:
         def compile_one(src):
             obj = os.path.join(objdir, os.path.splitext(src)[0] + ".o")
-            h = hashlib.sha256()
+            h = digest([src] + unit_deps(src))
             h.update(toolchain)
-            for d in [src] + headers.get(src, ["jtp_internal.h", "jtp_kernels.hip.h"]):
-                with open(os.path.join(CSRC, d), "rb") as fh:
-                    h.update(d.encode() + b"\0" + fh.read())
             # (the source id is compiled into the engine only: the other units do not change with it)
             tu_flags = [f for f in flags if not f.startswith("-DJTP_SOURCE_ID") or src == "jtp_engine.hip"]
             h.update(" ".join(tu_flags).encode())

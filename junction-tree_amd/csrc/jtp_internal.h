@@ -1,5 +1,5 @@
 // Internal structures shared by the host planner (jtp_plan.cpp), the kernels
-// (jtp_kernels.hip.h) and the C ABI (the engine's units: jtp_engine.h).  See DESIGN.md "Data layout in HBM".
+// (jtp_kernels.hip.h and the jtp_k_*.h units behind it) and the C ABI (the engine's units: jtp_engine.h).  See DESIGN.md "Data layout in HBM".
 //
 // Everything on the device is a *bit field*: a variable of cardinality k owns
 // ceil(log2 k) consecutive index bits of every table it appears in (tables are zero padded
@@ -160,7 +160,7 @@ struct JtTask {
     JtMsg msg[JT_MAX_MSG];     // [0, n_in) incoming; [JT_MAX_IN, JT_MAX_IN + n_out) outgoing
 };
 
-// Round 6: what a UNIT task of one outgoing message needs, and nothing else (jt_unit_lean, jtp_kernels.hip.h).  The generic pass
+// Round 6: what a UNIT task of one outgoing message needs, and nothing else (jt_unit_lean, jtp_k_lean.h).  The generic pass
 // interprets JtTask - 2.3 KB of record, bit-deposit loops over free_pos[] in scalar code for every staged entry, a branch per
 // message and row on e_dep: 1 200 scalar instructions per wave for a workgroup of 13 rows (profiles/r05_counters_c3.txt) - which is
 // what bounds a plan made of hundreds of thousands of such workgroups (BASELINE configs[2]).  Here the host has done the deposits:

@@ -2,7 +2,7 @@
 
 `jtp_plan_describe` exports every index table the HIP kernels consume (csrc/jtp_internal.h:
 JtTask / JtMsg).  This module executes those tables with numpy exactly the way
-csrc/jtp_kernels.hip.h `jt_pass` does - chunk decode, sub-box staging with partial-copy
+csrc/jtp_k_pass.h `jt_pass` does - chunk decode, sub-box staging with partial-copy
 summation, incremental A/R loop offsets, per-thread slot offsets, partial-copy flush - so
 that the planner (layouts, F/A/R split, message buffers, level schedule) can be checked
 against the oracle on machines without a GPU.  It is a checker of the *plan*, not a compute
@@ -164,7 +164,7 @@ class Emulator:
 
     # ---------------------------------------------------------------- one workgroup
     def _reduce_block(self, tk, chunk, record, strict):
-        """reduce task (csrc/jtp_kernels.hip.h jt_reduce): 256 entries of the sum of the partial copies"""
+        """reduce task (csrc/jtp_k_reduce.h jt_reduce): 256 entries of the sum of the partial copies"""
         assert tk["n_in"] == 1 and tk["n_out"] == 1 and tk["out"][0]["npart"] == 1
         src, dst = tk["in"][0], tk["out"][0]
         n = 1 << tk["nbits"]

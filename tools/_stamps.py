@@ -1,6 +1,6 @@
 """Shared by the time-stamp tools: run a few propagates on a plan made with JTP_DEBUG=2 under a library built with
 -DJT_STAMPS (python junction-tree_amd/build.py --out /tmp/stamps.so -DJT_STAMPS; JTPROP_LIB=/tmp/stamps.so) and read the
-workgroups' time stamps back.  Slots (jtp_kernels.hip.h, JT_STAMP): 0 entry, 1 first element loads issued, 2 end of the
+workgroups' time stamps back.  Slots (jtp_k_common.h, JT_STAMP): 0 entry, 1 first element loads issued, 2 end of the
 first staging attempt, 3 staged, 4 constants read, 5-8 after loop steps 0-3, 9 loop done, 10 epilogues done, 11 flush
 stores issued, 12 flush stores retired, 13 staging attempts."""
 import ctypes as C
