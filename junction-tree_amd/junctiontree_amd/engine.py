@@ -422,8 +422,9 @@ class Plan:
         the tree as it was given; sample i depends on (seed, i) and the beliefs only (`synthetic.sample_uniform`), so the first rows
         of a longer call are the rows of a shorter one.  Observed variables come out in their observed state.
 
-        Where samples meet a slice without mass (evidence of probability zero, tables that overflowed) `_capi.JtpError` is raised;
-        its `states` attribute holds the array, with -1 for the variables those samples could not draw."""
+        Where samples meet a slice without mass (evidence of probability zero, tables that overflowed) or a slice that holds a negative
+        or NaN belief entry (signed potentials: beliefs are then no distribution to draw from) `_capi.JtpError` is raised; its `states`
+        attribute holds the array, with -1 for the variables those samples could not draw - the other samples of the call are drawn."""
         n = int(n)
         if n < 1:
             raise ValueError("n = %d: at least one sample" % n)

@@ -282,7 +282,8 @@ class JunctionTree:
         {variable: observed state} - the samples are then draws from the posterior, with the observed variables in their
         observed states.  `normalize`: the propagate behind the samples runs on an overflow-safe plan (`engine.Plan(scaled=True)`),
         for models whose Z lies beyond float64.  Counter based: the same `seed` gives the same samples, and the first samples of a
-        longer call are those of a shorter one (`synthetic.sample_uniform`).
+        longer call are those of a shorter one (`synthetic.sample_uniform`).  The factor values must give non-negative beliefs: a draw
+        that meets a negative belief entry raises `_capi.JtpError` (its `states`: -1 for what could not be drawn), as one of probability zero does.
 
         The draw is one root-to-leaves sweep over the clique beliefs on the device (`engine.Plan.sample`), so every clique table is
         materialised: the plan is made without `cover`, unlike `propagate`'s.  On lattice-like models, whose cliques are mostly
@@ -330,7 +331,8 @@ class JunctionTree:
         where Z lies beyond float64; evidence of probability zero then raises `_capi.JtpError`.
 
         One propagate, then one upward sweep on the device over the cliques between the variables (`engine.Plan.joint`), where
-        clamping one variable to each of its states in turn costs a propagate per state.
+        clamping one variable to each of its states in turn costs a propagate per state.  A negative belief entry in one of those
+        cliques (signed factor values) raises `_capi.JtpError` naming the clique; cliques the sweep does not read may hold what they like.
 
         The sweep reads the clique beliefs, so every clique table is materialised: the plan is made without `cover`, unlike
         `propagate`'s.  On lattice-like models, whose cliques are mostly variables no factor of theirs covers, that is many times the
