@@ -228,10 +228,11 @@ int jtp_set_potential_products(jtp_plan *plan, int32_t batch, int32_t n_cliques,
 int jtp_fill_synthetic(jtp_plan *plan, int32_t batch, uint64_t seed, const double *scale);
 
 /* Hard evidence of one evidence set: variable var_ids[i] is observed in state states[i].  Replaces the
- * set's previous evidence (n = 0 clears it).  Equivalent to multiplying a one-hot indicator into one
- * clique that contains the variable (the equivalence tests/test_computation.py:411-459 of the
- * reference demonstrates for apply_evidence, computation.py:11-34), but nothing is rewritten: the kernels
- * skip the table entries that contradict the evidence.  Takes effect at the next jtp_propagate. */
+ * set's previous evidence (n = 0 clears it).  Hard evidence is slicing, as apply_evidence of the reference
+ * defines it (computation.py:11-34): in EVERY clique that contains the variable the entries that contradict
+ * the evidence are never used - whatever they hold, inf and NaN included - and nothing is rewritten.  On
+ * finite tables that equals a one-hot indicator multiplied into one such clique (the equivalence
+ * tests/test_computation.py:411-459 of the reference demonstrates).  Takes effect at the next jtp_propagate. */
 int jtp_set_evidence(jtp_plan *plan, int32_t batch, int32_t n, const int32_t *var_ids, const int32_t *states);
 
 /* ---- compute -------------------------------------------------------------------------- */

@@ -353,9 +353,11 @@ __device__ __forceinline__ void jt_mpass(const JtTask &tk, const JtBlock &bk, co
 #pragma unroll
                 for (int e = 0; e < NV; ++e) dst[k][e] = *reinterpret_cast<const double *>(reg + ad[k][e]);
         };
-        // A row that contradicts a set's evidence contributes nothing to that set: its factor rs (1.0 or 0.0,
-        // uniform) is the multiplier of the accumulating fma.  Two-stage pipeline over the sets: the entries of
-        // set s + 1 are requested before the products of set s are formed.
+        // A row that contradicts a set's evidence contributes nothing to that set: hard evidence is slicing, so the row never
+        // reaches the set's accumulators - a uniform branch on the set's bit of `rowok` skips it.  (A factor rs = 0.0 as the
+        // multiplier of the accumulating fma is not the same thing: 0 x inf = NaN where the contradicted row holds inf or NaN,
+        // or two finite entries whose product overflows.)  For a row that agrees rs is 1.0 and the arithmetic is what it was.
+        // Two-stage pipeline over the sets: the entries of set s + 1 are requested before the products of set s are formed.
         double psum = 0.0;
         if constexpr (ESUM) {
             psum = p[0] + p[1];
@@ -378,6 +380,9 @@ __device__ __forceinline__ void jt_mpass(const JtTask &tk, const JtBlock &bk, co
                 //  one more multiplication per set, not a select as well; without row evidence in the group - decided
                 //  once per workgroup - it is not there at all: 24 instead of 56 vector operations per row with two
                 //  incoming messages)
+                if constexpr (ROWEV) {
+                    if (!((rowok >> s) & 1u)) continue;              // (uniform: `rowok` is a ballot)
+                }
                 double t = 1.0;
                 if constexpr (ROWEV) t = __hiloint2double(__builtin_amdgcn_readfirstlane(((rowok >> s) & 1u) ? 0x3FF00000 : 0), 0);
                 if constexpr (NIN > 0 && !ROWEV) {
@@ -400,6 +405,7 @@ __device__ __forceinline__ void jt_mpass(const JtTask &tk, const JtBlock &bk, co
             for (int s = 0; s < G; ++s) {
                 load_set(s, cur);
                 if constexpr (ROWEV) {
+                    if (!((rowok >> s) & 1u)) continue;              // (uniform; the set's entries were requested, not used)
                     const double rs = __hiloint2double(__builtin_amdgcn_readfirstlane(((rowok >> s) & 1u) ? 0x3FF00000 : 0), 0);
 #pragma unroll
                     for (int e = 0; e < VEC; ++e) {

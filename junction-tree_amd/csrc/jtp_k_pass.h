@@ -700,6 +700,18 @@ __device__ __forceinline__ void jt_pass(const JtTask &tk, const JtBlock &bk, con
                 for (int e = 0; e < VEC; ++e) in[k][e] = t;
             }
         }
+        if constexpr (UNIT) {
+            // A unit clique's own values arrive as one more incoming table (the static table), so an entry that contradicts the
+            // evidence is cut out of the INPUTS: p = 0 alone would meet it in a product, and 0 x inf is NaN.  (Table-keeping
+            // cliques: p is the entry itself, replaced above; their inputs are messages, exactly 0 there and finite.)
+            if (ev_mask != 0) {                                // (uniform)
+#pragma unroll
+                for (int e = 0; e < VEC; ++e)
+#pragma unroll
+                    for (int k = 0; k < NIN; ++k)
+                        if (p[e] == 0.0) in[k][e] = 0.0;
+            }
+        }
         if constexpr (MODE == 0 && UNIT) {
             // a row that does not exist (uniform) adds nothing; without evidence an element is the product of its message
             // entries and nothing else (p = 1 is folded away: (1 * a) * b and a * b are the same double)

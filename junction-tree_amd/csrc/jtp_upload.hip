@@ -557,19 +557,20 @@ int jtp_set_evidence(jtp_plan *pl, int32_t batch, int32_t n, const int32_t *var_
         if (states[i] < 0 || states[i] >= hp.card[v]) return set_err(JTP_EINVAL, "evidence %d: state %d of variable %d (cardinality %d)", i, states[i], v, hp.card[v]);
         if (seen[v]) return set_err(JTP_EINVAL, "variable %d observed twice", v);
         seen[v] = 1;
-        // the indicator goes into ONE clique that contains the variable: the first in the caller's
-        // numbering (every rank makes the same choice; the owner applies it)
-        int host = -1;
-        for (int c = 0; c < hp.n_cliques && host < 0; ++c)
-            for (int u : hp.pn[c].vars)
-                if (u == v) host = c;
-        if (host < 0) return set_err(JTP_EINVAL, "variable %d is in no clique", v);
-        const PNode &p = hp.pn[host];
-        for (size_t j = 0; j < p.vars.size(); ++j)
-            if (p.vars[j] == v) {
-                ev[2 * host] |= ((1u << p.nb[j]) - 1u) << p.pos[j];
-                ev[2 * host + 1] |= (uint32_t)states[i] << p.pos[j];
-            }
+        // hard evidence is slicing: the mask goes into EVERY clique that contains the variable, so that no pass ever uses an
+        // entry that contradicts it - such an entry may hold inf or NaN, and a message that is exactly 0 there does not undo that
+        // (0 x inf).  Every rank fills the same table; a rank's kernels read the rows of the cliques it runs.
+        bool held = false;
+        for (int c = 0; c < hp.n_cliques; ++c) {
+            const PNode &p = hp.pn[c];
+            for (size_t j = 0; j < p.vars.size(); ++j)
+                if (p.vars[j] == v) {
+                    ev[2 * c] |= ((1u << p.nb[j]) - 1u) << p.pos[j];
+                    ev[2 * c + 1] |= (uint32_t)states[i] << p.pos[j];
+                    held = true;
+                }
+        }
+        if (!held) return set_err(JTP_EINVAL, "variable %d is in no clique", v);
     }
     HIP_TRY(hipSetDevice(hp.device));
     hipStream_t s = pl->streams[batch % pl->streams.size()];

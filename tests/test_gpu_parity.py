@@ -939,7 +939,8 @@ def test_hard_evidence_sets(share):
     """jtp_set_evidence: evidence sets that differ only by what is observed, with ONE copy of the clique
     tables (JTP_SHARE_POTENTIALS, BASELINE config 5 in miniature) or with a copy each.  Expected values:
     the oracle on potentials with a one-hot indicator multiplied into one clique containing the variable
-    (what apply_evidence amounts to, tests/test_computation.py:411-459 of the reference)."""
+    (equal to apply_evidence's slicing while every entry is finite, tests/test_computation.py:411-459 of the
+    reference; tables with inf or NaN at contradicted entries: tests/test_gpu_evidence_sliced.py)."""
     for spec, dtype in ((synthetic.wide_binary_tree(n_cliques=15, width=12, sep=6, card=2, seed=2), "f64"),
                         (synthetic.random_tree(n_cliques=9, width=5, sep=2, card=3, seed=4), "f64"),
                         (synthetic.wide_binary_tree(n_cliques=7, width=13, sep=6, card=2, seed=6), "f32")):
