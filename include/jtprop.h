@@ -315,6 +315,42 @@ int jtp_sample(jtp_plan *plan, int32_t batch, int32_t n_samples, uint64_t seed, 
  * and the message names the number of failed sets and the first. */
 int jtp_map(jtp_plan *plan, int32_t batch_begin, int32_t batch_end, int32_t *states, double *log_value);
 
+/* Max-propagation: the max-marginals of a request list for every evidence set in [batch_begin, batch_end).  A request is as in
+ * jtp_get_marginals - clique cliques[i], variables V_i = var_ids[var_off[i] .. var_off[i+1]) of that clique, in that axis order (none:
+ * one entry) - and its max-marginal is, for every assignment h of V_i, the largest prod_c psi_c(x) over the full assignments x that
+ * agree with h and with the set's evidence:
+ *     host[(b - batch_begin) * set_stride + out_off[i] + h] = that value times 2^-S   (doubles, C order; 0 where h contradicts the evidence)
+ *     log2_scale[(b - batch_begin) * n + i] = S, an exponent per (set, clique)
+ *     log_value (NULL, or [batch_end - batch_begin]) = what jtp_map reports for the set, bit for bit: it is the same computation.
+ * The largest entry of every request table of a set times 2^S is the value of the set's most probable assignment.  No propagate is
+ * needed, beliefs and messages are not touched; the evidence is what jtp_set_evidence last gave each set.
+ * The sweep runs on the schedule of jtp_sample / jtp_map (by depth, then clique number; K_c = the variables clique c shares with its
+ * parent clique, F_c the others in host axis order; children in ascending clique number), float64 throughout, and only entries that
+ * agree with the evidence are looked at.  Upward, deepest first, jtp_map's pass as it stands: raw_c[k] = max_r ((double)psi_c[k, r] *
+ * m_1) * m_2 ..., e_c = ilogb(max raw_c), m_c = ldexp(raw_c, -e_c).  Downward, shallowest first (the root has no parent message):
+ * for clique c and each child d,
+ *     rawdn_d[k_d] = max over the entries (k, r) of c that agree with k_d of ((psi_c[k, r] * D_c[k]) * m_d1) * m_d2 ...
+ * - the parent's message D_c first (absent at the root), then the children of c in ascending clique number WITHOUT d; k_d indexed
+ * as raw_d is; 0 where k_d contradicts the evidence -, f_d = ilogb(max rawdn_d), D_d = ldexp(rawdn_d, -f_d).  A request on clique c:
+ *     out[h] = max over the entries of c that agree with h of ((psi_c[k, r] * D_c[k]) * m_d1) * m_d2 ...     all children of c this time.
+ * The exponents are added up on the host as integers: U_d = e_d + sum of U_x over the children x of d; V_root = 0, V_d = V_c + (sum
+ * of U_s over the siblings s != d) + f_d; S_c = V_c + sum of U_d over the children d of c.  A maximum is exact whatever the order and
+ * the order of the multiplications is fixed above, so nothing depends on the plan's layout, compaction, root or launch flags, nor on
+ * how r is cut into segments or the sets into chunks: equal potentials and evidence give bit-equal tables and exponents.
+ * All sets of a chunk go through the same launches - jtp_map's upward ones, one per depth over the downward messages into that depth,
+ * one over all requests -; a chunk is as many sets as keep the work area (raw and arg tables, down tables, segment results, maxima,
+ * evidence rows, request outputs) under 64 MiB.  The records of the last request list are kept with the plan.  A task per (clique,
+ * child) multiplies all but one of the clique's incoming messages into every entry: the downward pass is quadratic in the children
+ * of one clique.
+ * Works where jtp_map works: plans of one set, of n_batch sets and with JTP_SHARE_POTENTIALS, float32 and float64 tables, any layout.
+ * JTP_EUNSUPPORTED: JTP_MULTISET plans, n_ranks > 1, plans in which a clique keeps no table (cover_*).  JTP_EINVAL: a bad range, a
+ * request variable that is not in its clique or is listed twice, entries that do not fit set_stride, null arguments.  A set FAILS
+ * where an entry that agrees with its evidence is negative or NaN, or where a maximum that feeds a message (max raw_c, max rawdn_d) is
+ * zero or not finite (evidence of probability zero): its tables are all 0, its exponents 0, its log_value -inf; every set of the range
+ * is still written, the call returns JTP_EINVAL and the message names the number of failed sets and the first. */
+int jtp_max_marginals(jtp_plan *plan, int32_t batch_begin, int32_t batch_end, int32_t n, const int32_t *cliques, const int32_t *var_off,
+                      const int32_t *var_ids, const int64_t *out_off, int64_t set_stride, double *host, int64_t *log2_scale, double *log_value);
+
 /* The joint of n_query distinct variables that need not share a clique, from the beliefs of the last propagate of evidence set
  * `batch`: host[] = the table over var_ids[0 .. n_query) in that axis order (doubles, C order).  Unnormalised in the sense of
  * jtp_get_marginal: it sums to Z, and on a JTP_SCALED plan it is the true table times 2^-E, E the exponent of the TOP clique below
@@ -385,7 +421,8 @@ int jtp_debug_read_msg(jtp_plan *plan, int32_t batch, int64_t off, int64_t n, do
 /* Test hooks.  knob "flow_debug": JtFlow::dbg of the following propagates (8 = every dataflow wait times
  * out after 20 ms: exercises the fall-back to one launch per level); "flow": 0 = launch per level from now on;
  * "fail_alloc": see jtp_debug_live_bytes; "acc_chunk": evidence sets per chunk of jtp_accumulate_marginals (0: by size);
- * "map_chunk": the same of jtp_map; "map_seg": entries of r a wave of jtp_map takes (0: the default; the result does not depend on it). */
+ * "map_chunk": the same of jtp_map and jtp_max_marginals; "map_seg": entries of r a wave of jtp_map and of jtp_max_marginals takes
+ * (0: the default; the result does not depend on it). */
 int jtp_debug_set(jtp_plan *plan, const char *knob, int64_t value);
 /* Test hook: bytes of device memory and of pinned host memory the library holds right now, process-wide (every plan's buffers;
  * either pointer may be NULL).  With knob "fail_alloc" of jtp_debug_set (the N-th allocation of the plan from now on reports

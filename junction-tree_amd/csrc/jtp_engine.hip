@@ -392,8 +392,9 @@ int jtp_debug_set(jtp_plan *pl, const char *knob, int64_t value) {
     else if (!strcmp(knob, "flow")) pl->flow = value != 0 && !pl->hp.segments.empty();
     else if (!strcmp(knob, "fail_alloc")) pl->mem.fail_in = std::max<int64_t>(value, 0);      // (MemLedger::fail_in)
     else if (!strcmp(knob, "acc_chunk")) pl->acc_chunk = std::max<int64_t>(value, 0);         // (jtp_accumulate_marginals; 0: by size)
-    else if (!strcmp(knob, "map_chunk")) pl->map_chunk = std::max<int64_t>(value, 0);         // (jtp_map; 0: by size)
-    else if (!strcmp(knob, "map_seg")) pl->map_seg = std::max<int64_t>(value, 0), pl->map = MapMem(&pl->mem);      // (jtp_map: the records are built again)
+    else if (!strcmp(knob, "map_chunk")) pl->map_chunk = std::max<int64_t>(value, 0);         // (jtp_map, jtp_max_marginals; 0: by size)
+    else if (!strcmp(knob, "map_seg"))                                                        // (jtp_map, jtp_max_marginals: the records are built again)
+        pl->map_seg = std::max<int64_t>(value, 0), pl->map = MapMem(&pl->mem), pl->maxm = MaxMem(&pl->mem);
     else return set_err(JTP_EINVAL, "unknown knob %s", knob);
     return JTP_OK;
 }

@@ -61,7 +61,7 @@ struct JtMap {
 struct JtMapChild {
     int64_t raw_off;                 // the child's place in a set's raw table
     int32_t ord;                     // the child's record
-    int32_t pad;
+    int32_t down;                    // jtp_max_marginals: 1 = the input is the clique's own downward table D (down tables are laid out as raw ones); jtp_map: 0
     uint32_t stride[JT_MAX_VARS];    // per variable v[j] of the PARENT's record: its weight in the child's k (0: not shared with the child)
 };
 // what jtp_map keeps with the plan: the records (built once) and the work area of one chunk of evidence sets (grow-only) - per set
@@ -76,6 +76,42 @@ struct MapMem {
     std::vector<int64_t> depth_items;    // per depth: most (k, segment) pairs of a clique
     std::vector<char> depth_merge;       // ... and whether some clique there is cut into segments
     explicit MapMem(MemLedger *m) : recs(m), kids(m), depth_begin(m), work(m) {}
+};
+
+// jtp_max_marginals: one record per table the downward half of max-propagation forms by a maximum over a clique c's entries - the
+// downward message to a child d of c (one per clique but the root, in the visit order of d) and a request (clique c, variables V).
+// v[0, nK): the variables of the output - K_d with the weights raw_d has, or V in the requested order, C order -; v[nK, nK + nF):
+// the clique's other variables in host axis order, `radix` their weight in r; all of them as clique c stores them (jt_query_var).
+// The inputs are multiplied in list order: the clique's own downward table D_c first (JtMapChild::down; absent at the root), then
+// the upward messages of the children of c in ascending clique number - all of them for a request, all but d for the message to d.
+// An input's stride[j] is the weight of v[j] in that table's index.  Segments as for JtMap.
+struct JtMax {
+    int64_t psi_off;                 // element offset of the table of clique c in the potential arena
+    int64_t out_off;                 // ord >= 0: the place of D_d in a set's down tables (= raw_off of d); else the request's place in a set's outputs
+    int64_t part_off;                // nseg > 1: place in a set's segment results (entry k * nseg + seg)
+    int32_t nK, nF;
+    uint32_t R, nk;                  // products of the cardinalities of F and of K
+    uint32_t nseg;
+    int32_t ord;                     // the record of d - the slot of the largest entry of rawdn_d - or -1: a request
+    int32_t in_begin, in_end;        // the inputs: a range of a JtMapChild array
+    JtSampleVar v[JT_MAX_VARS];
+};
+// what jtp_max_marginals keeps with the plan, grow-only: the downward records (built once), the records of the last request list and
+// that list (n, cliques, var_off, var_ids), and the work area of one chunk of evidence sets - jtp_map's (raw, arg, maxima, evidence
+// rows, flags), then the down tables, the maxima of theirs, the segment results and the request outputs
+struct MaxMem {
+    DeviceBuf<JtMax> down, req;
+    DeviceBuf<JtMapChild> down_in, req_in;
+    DeviceBuf<char> work;
+    bool built = false;              // `down` holds the plan's records (a tree of one clique has none)
+    std::vector<int32_t> key;        // the request list `req` was made from
+    std::vector<int64_t> req_out;    // [n + 1]: the requests' places in a set's outputs
+    int64_t down_parts = 0, req_parts = 0;       // per set: segment results of the downward records, of the requests
+    int64_t req_items = 1;               // most (entry, segment) pairs of a request
+    char req_merge = 0;                  // ... and whether some request is cut into segments
+    std::vector<int64_t> depth_items;    // per depth >= 1 (entry d - 1): most (k, segment) pairs of a message into that depth
+    std::vector<char> depth_merge;
+    explicit MaxMem(MemLedger *m) : down(m), req(m), down_in(m), req_in(m), work(m) {}
 };
 
 // jtp_joint: one record per ACTIVE clique of a query (the cliques on the paths from the query variables' homes up to the top), in

@@ -461,6 +461,43 @@ class Plan:
         _capi.check(rc)
         return states, value
 
+    def max_marginals(self, requests, batch_begin=0, batch_end=None):
+        """Max-propagation (`jtp_max_marginals`): for `requests` = [(clique, labels), ...] and every evidence set in [batch_begin,
+        batch_end) the max-marginal of the clique onto `labels` - per assignment of those variables, the value of the best full
+        assignment that agrees with it and with the set's evidence.  Returns (tables, log2_scale, log_value): `tables[b][i]` a float64
+        array of the request's shape, the true table times 2**-log2_scale[b, i] (int64 (n_sets, n): the sweep takes powers of two
+        out of its messages, so nothing overflows); `log_value` float64 (n_sets,), what `map` reports for the set, bit for bit.
+        An upward and a downward max-product sweep over the staged potentials, all sets through the same launches: no propagate
+        is needed, and what one left is not touched.  Equal potentials and evidence give bit-equal tables whatever the plan's layout.
+
+        Where sets have no assignment of positive finite value `_capi.JtpError` is raised; its `tables`, `log2_scale` and `log_value`
+        attributes hold the results, with zeros and -inf for those sets."""
+        end = self.n_batch if batch_end is None else int(batch_end)
+        begin = int(batch_begin)
+        n_sets = max(end - begin, 0)
+        n = len(requests)
+        cliques = _int_array([self.abi_of[c] for c, _ in requests] + [0])
+        var_off, var_ids, out_off, shapes = [0], [], [0], []
+        for _, labels in requests:
+            var_ids += [self.var_id[lab] for lab in labels if lab not in self._trivial]
+            var_off.append(len(var_ids))
+            shape = tuple(1 if lab in self._trivial else self.card[self.var_id[lab]] for lab in labels)
+            shapes.append(shape)
+            out_off.append(out_off[-1] + (int(np.prod(shape, dtype=np.int64)) if shape else 1))
+        keep = (cliques, _int_array(var_off), _int_array(var_ids + [0]), (C.c_int64 * (n + 1))(*out_off))
+        flat = np.zeros((n_sets, out_off[-1]), dtype=np.float64)
+        scale = np.zeros((n_sets, n), dtype=np.int64)
+        value = np.zeros(n_sets, dtype=np.float64)
+        rc = self._lib.jtp_max_marginals(self._handle, begin, end, n, *[C.addressof(k) for k in keep], out_off[-1],
+                                         flat.ctypes.data_as(C.c_void_p), scale.ctypes.data_as(C.c_void_p), value.ctypes.data_as(C.c_void_p))
+        tables = [[flat[b, out_off[i]:out_off[i + 1]].reshape(shapes[i]) for i in range(n)] for b in range(n_sets)]
+        if rc == _capi.JTP_EINVAL and n_sets > 0 and bool(np.isneginf(value).any()):
+            err = _capi.JtpError(self._lib.jtp_last_error().decode("utf-8", "replace"))
+            err.tables, err.log2_scale, err.log_value = tables, scale, value
+            raise err
+        _capi.check(rc)
+        return tables, scale, value
+
     def joint(self, variables, batch=0):
         """The joint of `variables` - distinct labels that need not share a clique - from the beliefs of the last propagate of evidence
         set `batch` (`jtp_joint`): (float64 array with one axis per variable, in the order given, log2_scale).  Unnormalised, as

@@ -396,14 +396,32 @@ class JunctionTree:
         The sweep reads every clique table, so every clique table is materialised: the plan is made without `cover`, unlike
         `propagate`'s.  On lattice-like models, whose cliques are mostly variables no factor of theirs covers, that is many times the
         memory - 9 GiB for the 6 x 167 lattice of cardinality 8 (BASELINE configs[2]) against the few MiB `propagate` needs."""
+        sizes = self.clique_tree.factor_graph.sizes
+        n_sets = len(evidence_sets)
+        if n_sets == 0:
+            return {lab: np.zeros(0, dtype=np.int32) for lab in sizes}, np.zeros(0)
+
+        def sweep(plan):
+            try:
+                states, value = plan.map(0, n_sets)
+            except Exception as exc:
+                if hasattr(exc, "states"):
+                    exc.states = self._map_columns(plan, exc.states, sizes)
+                raise
+            return self._map_columns(plan, states, sizes), value
+
+        return self._on_map_plan(values, evidence_sets, sweep)
+
+    def _on_map_plan(self, values, evidence_sets, sweep):
+        """`sweep(plan)` on the plan the max-product calls share (`map_evidence_sets`, `max_propagate_evidence_sets`): one copy of the
+        clique tables, an evidence set per entry of the non-empty `evidence_sets`; the factor values staged, the evidence set, and
+        cleared again whatever happens."""
         import weakref
         from . import engine
 
         ct = self.clique_tree
         sizes = ct.factor_graph.sizes
         n_sets = len(evidence_sets)
-        if n_sets == 0:
-            return {lab: np.zeros(0, dtype=np.int32) for lab in sizes}, np.zeros(0)
         all_f32 = all(type(x) is np.ndarray and x.dtype == np.float32 for x in values)
         dtype = "f32" if all_f32 else "f64"
         # (an entry of its own, as `sample` keeps: what `propagate(xs, changed=...)` trusts about "plan" is never said of this plan)
@@ -418,17 +436,63 @@ class JunctionTree:
         try:
             for b, observed in enumerate(evidence_sets):
                 plan.set_evidence(dict(observed) if observed else {}, batch=b)
-            try:
-                states, value = plan.map(0, n_sets)
-            except Exception as exc:
-                if hasattr(exc, "states"):
-                    exc.states = self._map_columns(plan, exc.states, sizes)
-                raise
+            return sweep(plan)
         finally:
             for b, observed in enumerate(evidence_sets):     # (the plan is the cache's: whoever is handed it next finds no evidence set)
                 if observed:
                     plan.set_evidence({}, batch=b)
-        return self._map_columns(plan, states, sizes), value
+
+    def max_propagate(self, values, evidence=None):
+        """Max-propagation (not in the reference): (list, log_value) - per factor a float64 array of the factor's shape holding the
+        LOG of its unnormalised max-marginal: for every assignment of the factor's variables the log of the product of the factor
+        values at the best full assignment that agrees with it and with `evidence` ({variable: observed state}); -inf where no
+        assignment of positive value does.  Every array's maximum is `log_value`, the log value of the most probable assignment
+        (`map`): an entry's distance below it says how much worse the best explanation gets when those variables are held there,
+        and a variable whose max-marginal has two entries at the maximum has no unique most probable state.
+        See `max_propagate_evidence_sets`."""
+        tables, value = self.max_propagate_evidence_sets(values, [dict(evidence) if evidence else {}])
+        return tables[0], float(value[0])
+
+    def max_propagate_evidence_sets(self, values, evidence_sets):
+        """`max_propagate` for several evidence sets over the same factor values: (one list of arrays per set, float64 array of the
+        sets' log values), all sets through the same launches of one upward and one downward max-product sweep on the device
+        (`engine.Plan.max_marginals`) - where clamping every variable to every state in turn costs sum(cardinalities) sweeps of
+        `map`.  It runs on the plan `map_evidence_sets` makes (every clique table materialised).  The sweep rescales its messages by
+        powers of two; the logarithm is np.log(table) + log2_scale * np.log(2.0), so models whose values lie beyond float64 need
+        nothing special.  A set whose evidence has probability zero raises `_capi.JtpError`, carrying `max_marginals` (all -inf for
+        that set) and `log_value` (-inf)."""
+        ct = self.clique_tree
+        n_sets = len(evidence_sets)
+        if n_sets == 0:
+            return [], np.zeros(0)
+        requests = [(ct.factor_to_maxclique[f], list(labels)) for f, labels in enumerate(ct.factor_graph.factors)]
+
+        def logs(tables, scale):
+            with np.errstate(divide="ignore"):
+                return [[np.log(t) + float(e) * np.log(2.0) for t, e in zip(tables[b], scale[b])] for b in range(n_sets)]
+
+        def sweep(plan):
+            try:
+                tables, scale, value = plan.max_marginals(requests, 0, n_sets)
+            except Exception as exc:
+                if hasattr(exc, "tables"):
+                    exc.max_marginals = logs(exc.tables, exc.log2_scale)
+                raise
+            return logs(tables, scale), value
+
+        return self._on_map_plan(values, evidence_sets, sweep)
+
+    def max_marginals(self, values, evidence=None):
+        """{variable: float64 vector}: the log max-marginal of every variable - entry s is the log value of the best full
+        assignment with the variable in state s (and `evidence` observed), -inf where there is none.  Taken on the host from one
+        factor of `max_propagate` that holds the variable, by a maximum over its other axes: exact."""
+        tables, _ = self.max_propagate(values, evidence)
+        out = {}
+        for labels, table in zip(self.clique_tree.factor_graph.factors, tables):
+            for ax, lab in enumerate(labels):
+                if lab not in out:
+                    out[lab] = table.max(axis=tuple(a for a in range(table.ndim) if a != ax))
+        return out
 
     @staticmethod
     def _map_columns(plan, states, sizes):
