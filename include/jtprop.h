@@ -351,6 +351,44 @@ int jtp_map(jtp_plan *plan, int32_t batch_begin, int32_t batch_end, int32_t *sta
 int jtp_max_marginals(jtp_plan *plan, int32_t batch_begin, int32_t batch_end, int32_t n, const int32_t *cliques, const int32_t *var_off,
                       const int32_t *var_ids, const int64_t *out_off, int64_t set_stride, double *host, int64_t *log2_scale, double *log_value);
 
+/* The m most probable PAIRWISE DISTINCT full assignments of evidence set `batch` (the evidence jtp_set_evidence last gave it), in
+ * descending value, by one upward max-product sweep whose message entries carry lists, and a decode per solution:
+ *     states[s * n_vars + v] = state of variable v in solution s (a variable of no clique: 0)
+ *     log_value[s] = log of the solution's unnormalised value prod_c psi_c(x)
+ *     *n_found <= m = how many assignments of positive value there are; rows s >= *n_found are all -1, their log_value -inf, and
+ *                     the call is still JTP_OK.
+ * No propagate is needed, beliefs and messages are not touched.  1 <= m <= JTP_MBEST_MAX.
+ * The sweep runs on the schedule of jtp_sample / jtp_map (by depth, then clique number; K_c = the variables clique c shares with its
+ * parent clique, F_c the others in host axis order, R_c = prod card(F_c); children in ascending clique number), float64 throughout.
+ * Upward, deepest first: every clique c and every assignment k of K_c gets a list raw_c[k][0..M) - non-increasing, zero past its
+ * count, all zero where k contradicts the evidence - with a place (r, t) per element.  A child's message is read as m_d[k_d][j] =
+ * ldexp(raw_d[k_d][j], -e_d), e_d = ilogb(max over k of raw_d[k][0]); element 0 of every list is jtp_map's raw, so the exponents
+ * are jtp_map's.  Per entry (k, r) that agrees with the evidence, a fold over the children d_1, d_2, ...:
+ *     E_0 = [(double)psi_c[k, r]]   (empty if that is 0)
+ *     E_i = the M largest of the products E_{i-1}[a] * m_{d_i}[k_{d_i}][b] that are > 0, in descending value, equal values in ascending
+ *           (a, b), lexicographically; every element remembers its (a, b)
+ * (multiplication by a non-negative number is monotone, so only pairs with (a + 1) * (b + 1) <= M can be among them, and the order
+ * among equals agrees with leaving the others out).  Per k, raw_c[k] = the M largest elements of the lists E_last of all such r, in
+ * descending value, equal values in ascending (r, t), t the element's place in its list.  That is a total order: how r is cut into
+ * lanes and segments does not matter.  Downward, per solution s: rank[root] = s; clique c reads (r, t) at (k from the digits written
+ * above it, rank[c]), writes the digits of F_c from r, and follows element t of entry (k, r) back through the fold - the b of the
+ * last step is the rank of the last child, its a the element of the step before, and so on; the device forms that one entry's
+ * fold again, same operations in the same order, rather than keep a rank per child with every element.
+ * log_value[s] = log(raw_root[0][s]) + ln 2 * (sum of e_c over the other cliques).
+ * So: solution 0 of any call is jtp_map's result bit for bit, ties included; the first m' solutions of a call with m are the call with
+ * m' < m (an element with a >= m' or b >= m' has m' elements before it) - the device runs lists of 1, 4 or 16 elements, the
+ * smallest that holds m -; different ranks at one (clique, k) are different sub-assignments; an assignment whose scaled value
+ * underflows to 0 is not listed; nothing depends on the plan's layout, compaction, root, launch flags, the "map_seg" knob or the
+ * table type beyond the numbers held.
+ * Works where jtp_map works: plans of one set, of n_batch sets and with JTP_SHARE_POTENTIALS, float32 and float64 tables, any layout;
+ * the work area is that of one set, kept with the plan, grow-only.
+ * JTP_EUNSUPPORTED: JTP_MULTISET plans, n_ranks > 1, plans in which a clique keeps no table (cover_*).  JTP_EINVAL: m < 1, m >
+ * JTP_MBEST_MAX, a bad batch, null arguments.  The set FAILS as in jtp_map - an entry that agrees with its evidence is negative or
+ * NaN, or a clique's largest first element is zero or not finite (evidence of probability zero) -: all m rows are -1, every log_value
+ * -inf, *n_found = 0, the call returns JTP_EINVAL and the message says so. */
+#define JTP_MBEST_MAX 16
+int jtp_map_best(jtp_plan *plan, int32_t batch, int32_t m, int32_t *states, double *log_value, int32_t *n_found);
+
 /* The joint of n_query distinct variables that need not share a clique, from the beliefs of the last propagate of evidence set
  * `batch`: host[] = the table over var_ids[0 .. n_query) in that axis order (doubles, C order).  Unnormalised in the sense of
  * jtp_get_marginal: it sums to Z, and on a JTP_SCALED plan it is the true table times 2^-E, E the exponent of the TOP clique below

@@ -5,7 +5,8 @@
 //   jtp_readout.hip    beliefs, marginals, scale / Z / log Z, expected counts
 //   jtp_sample.hip     jtp_sample: joint posterior samples from the beliefs a propagate left        (these three: the queries on the sampling
 //                      schedule; jtp_query.h has their records and the table walk, child staging and launch shape they share)
-//   jtp_map.hip        jtp_map: the most probable assignment (max-product sweep over the potentials); jtp_max_marginals: max-propagation
+//   jtp_map.hip        jtp_map: the most probable assignment (max-product sweep over the potentials); jtp_max_marginals: max-propagation;
+//                      jtp_map_best: the M most probable assignments
 //   jtp_joint.hip      jtp_joint: the joint of variables of different cliques, from the beliefs a propagate left
 //   jtp_profile.cpp    profiling, regions, statistics;    jtp_comm.cpp   RCCL and roctx loaders, jtp_comm_*, the exchange steps
 // Every global has one definition, in the unit that owns it; the other units reach it through the functions declared here.
@@ -241,6 +242,7 @@ struct jtp_plan {
     int64_t map_chunk = 0;
     int64_t map_seg = 0;            // jtp_debug_set "map_seg": entries per segment of r (0: JT_QUERY_SEG); setting it drops the records
     MaxMem maxm{&mem};              // jtp_max_marginals: downward and request records, work area (both knobs govern it too)
+    MbestMem mbest{&mem};           // jtp_map_best: work area of one set (jtp_map's records; "map_seg" governs it too)
     JointMem joint{&mem};           // jtp_joint: records and work area
     hipStream_t eval_stream = nullptr;   // stream whose kernels may still read the buffer
     bool eval_pending = false;

@@ -114,6 +114,14 @@ struct MaxMem {
     explicit MaxMem(MemLedger *m) : down(m), req(m), down_in(m), req_in(m), work(m) {}
 };
 
+// what jtp_map_best keeps with the plan beside jtp_map's records (which it reads as they stand), grow-only: the work area of one
+// evidence set - per assignment of K_c a list of `cap` values and as many places (r, t), the same per segment result, the cliques'
+// maxima, the evidence row, and per solution a state row, the rank it takes of every clique's list and the fold's back-pointers
+struct MbestMem {
+    DeviceBuf<char> work;
+    explicit MbestMem(MemLedger *m) : work(m) {}
+};
+
 // jtp_joint: one record per ACTIVE clique of a query (the cliques on the paths from the query variables' homes up to the top), in
 // visit order - the top first - built and uploaded per call.  v[0, nK): the variables shared with the parent clique, `radix` their
 // C-order weight in k; v[nK, nK + nQ): the query variables whose home the clique is (their digits come from x);

@@ -461,6 +461,27 @@ class Plan:
         _capi.check(rc)
         return states, value
 
+    def map_best(self, m, batch=0):
+        """The `m` most probable pairwise distinct joint assignments of evidence set `batch`, best first (`jtp_map_best`, 1 <= m <=
+        16): an int32 array (n_found, len(self.var_labels)) and a float64 array (n_found,) of their unnormalised log values;
+        n_found < m where fewer assignments have a positive value.  Row 0 is what `map` returns for the set, bit for bit, and the
+        first rows of a longer call are the rows of a shorter one.  One upward max-product sweep over the staged potentials whose
+        message entries carry lists, and a decode per solution: no propagate is needed, and what one left is not touched.
+
+        Where the set has no assignment of positive finite value `_capi.JtpError` is raised, as `map` raises it; its `states` (m rows
+        of -1) and `log_value` (-inf) attributes hold the arrays."""
+        m = int(m)
+        states = np.zeros((max(m, 0), len(self.var_labels)), dtype=np.int32)
+        value = np.zeros(max(m, 0), dtype=np.float64)
+        found = C.c_int32(-1)
+        rc = self._lib.jtp_map_best(self._handle, int(batch), m, states.ctypes.data_as(C.c_void_p), value.ctypes.data_as(C.c_void_p), C.byref(found))
+        if rc == _capi.JTP_EINVAL and found.value == 0 and m > 0 and bool(np.isneginf(value).all()):
+            err = _capi.JtpError(self._lib.jtp_last_error().decode("utf-8", "replace"))
+            err.states, err.log_value = states, value
+            raise err
+        _capi.check(rc)
+        return states[:found.value], value[:found.value]
+
     def max_marginals(self, requests, batch_begin=0, batch_end=None):
         """Max-propagation (`jtp_max_marginals`): for `requests` = [(clique, labels), ...] and every evidence set in [batch_begin,
         batch_end) the max-marginal of the clique onto `labels` - per assignment of those variables, the value of the best full

@@ -412,6 +412,26 @@ class JunctionTree:
 
         return self._on_map_plan(values, evidence_sets, sweep)
 
+    def map_best(self, values, m, evidence=None):
+        """The `m` most probable pairwise distinct joint assignments (1 <= m <= 16), best first: a list of ({variable: state},
+        log_value), shorter than `m` where fewer assignments have a positive value; its first entry is what `map` returns.  One
+        sweep on the device (`engine.Plan.map_best`) on the plan `map` makes - where clamping and re-running `map` along a partition
+        of the assignments costs about m x cliques sweeps.  Evidence of probability zero raises `_capi.JtpError`, carrying `states`
+        ({variable: int32 array of m times -1}) and `log_value` (-inf)."""
+        sizes = self.clique_tree.factor_graph.sizes
+
+        def sweep(plan):
+            try:
+                states, value = plan.map_best(m)
+            except Exception as exc:
+                if hasattr(exc, "states"):
+                    exc.states = self._map_columns(plan, exc.states, sizes)
+                raise
+            cols = self._map_columns(plan, states, sizes)
+            return [({lab: int(col[s]) for lab, col in cols.items()}, float(value[s])) for s in range(len(value))]
+
+        return self._on_map_plan(values, [dict(evidence) if evidence else {}], sweep)
+
     def _on_map_plan(self, values, evidence_sets, sweep):
         """`sweep(plan)` on the plan the max-product calls share (`map_evidence_sets`, `max_propagate_evidence_sets`): one copy of the
         clique tables, an evidence set per entry of the non-empty `evidence_sets`; the factor values staged, the evidence set, and
