@@ -414,6 +414,36 @@ int jtp_map_best(jtp_plan *plan, int32_t batch, int32_t m, int32_t *states, doub
  * still written, the call returns JTP_EINVAL and the message names the number of such (clique, k) pairs and the first clique. */
 int jtp_joint(jtp_plan *plan, int32_t batch, int32_t n_query, const int32_t *var_ids, double *host, int64_t *log2_scale);
 
+/* Entropy of the posterior of every evidence set in [batch_begin, batch_end), and its cross-entropy against another propagated set
+ * of the plan, in nats, from the beliefs the last propagates left: one streaming pass over ALL belief tables on the device.
+ * On the schedule of jtp_sample (by depth, then clique number), for clique c: K_c = the variables c shares with its parent clique
+ * (none at the root), F_c the others, R_c = prod card(F_c), n_c the entries of c; beta_c^b the belief of c in set b as the last
+ * propagate left it, widened to float64 before anything else, entries that contradict the evidence already 0 in it;
+ *     sigma_c[k] = sum_r beta_c[k, r],    S_c = sum_k sigma_c[k],
+ * and for a set a and a reference set b (b = a: entropy)
+ *     t_c(a, b) = sum_k [ sum_r beta_c^a[k, r] ln beta_c^b[k, r]  -  sigma_c^a[k] ln sigma_c^b[k] ].
+ * Terms with beta_c^a = 0 (sigma_c^a[k] = 0) are left out - not multiplied: the logarithm is never taken of 0 on their account.
+ *     h_c = -t_c(a, a) / S_c^a = H(F_c | K_c) under the posterior of a, >= 0;   x_c = -t_c(a, b) / S_c^a, the same conditional
+ * cross-entropy against b, +inf (no error) where some beta^a > 0 meets beta^b = 0;   H(a) = sum_c h_c by the chain rule on the
+ * tree - it depends neither on the root nor on the schedule, the single h_c do -;   X(a, b) = sum_c x_c;   KL(a || b) = X - H >= 0.
+ * The power of two a JTP_SCALED plan keeps per node cancels inside t_c / S_c, for a and for b: no exponent is read.
+ * entropy[batch_end - batch_begin]: H of each set.  ref_set and cross: both NULL, or ref_set[i] = the set b for set batch_begin + i
+ * (any propagated set of the plan, inside the range or not) and cross[i] = X.  clique_entropy: NULL, or [sets x n_cliques], h_c by
+ * clique number.  Beliefs and messages are not touched.  Works where jtp_sample works: one set or n_batch sets,
+ * JTP_SHARE_POTENTIALS, float32 and float64 tables, every layout policy, compaction and launch flag, JTP_SCALED.
+ * Every entry is read once (with a reference: once from each table).  The lanes of a wave take interleaved indices of F_c listed
+ * in ascending DEVICE stride, so that they read consecutive elements; the order of a sum therefore depends on the stored layout:
+ * plans of different layout agree to rounding - a few ulps times the length of the longest chain of additions, times max |ln beta| -
+ * NOT bit for bit.  Two calls on the same plan and beliefs agree bit for bit: no floating-point atomics, no order that depends on
+ * timing.  The cliques' terms are added in visit order.
+ * JTP_EUNSUPPORTED, in jtp_sample's words: JTP_MULTISET plans, n_ranks > 1, plans in which a clique keeps no table (cover_*).
+ * JTP_EINVAL before any device work: a bad range, entropy NULL, only one of ref_set and cross, a ref_set out of range, a set or
+ * reference set never propagated.  A set FAILS where it or its reference holds a negative or NaN belief entry, or where an S_c of
+ * it is zero or not finite (evidence of probability zero, overflow without JTP_SCALED): its outputs are NaN, every other set is
+ * still written, the call returns JTP_EINVAL and the message names the number of failed sets and the first (set, clique). */
+int jtp_entropy(jtp_plan *plan, int32_t batch_begin, int32_t batch_end, const int32_t *ref_set, double *entropy, double *cross,
+                double *clique_entropy);
+
 /* Expected counts: the weighted sum over evidence sets [batch_begin, batch_end) of the NORMALISED marginals of a request list
  * (requests as in jtp_get_marginals), formed and accumulated on the device:
  *     host[out_off[i] + h] = sum_b  weights[b - batch_begin] * m_bi[h] / S_bi ,   S_bi = sum_h m_bi[h]

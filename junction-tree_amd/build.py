@@ -20,7 +20,9 @@ INST = ["jtp_inst_%s_%s.hip" % (fam, t) for fam in ("both", "bothm", "level", "m
 ENGINE = ["jtp_engine.hip", "jtp_upload.hip", "jtp_propagate.hip", "jtp_readout.hip", "jtp_sample.hip", "jtp_map.hip", "jtp_joint.hip", "jtp_profile.cpp", "jtp_comm.cpp"]
 # (the planner's units, pure host C++: csrc/jtp_plan_build.h has the map)
 PLANNER = ["jtp_plan.cpp", "jtp_plan_layout.cpp", "jtp_plan_loops.cpp", "jtp_plan_tasks.cpp", "jtp_plan_schedule.cpp", "jtp_plan_json.cpp"]
-SOURCES = PLANNER + ENGINE + INST                # (compiled in parallel, one object each, then linked)
+# (query units added since the engine's list was fixed at nine: csrc/jtp_query.h has their records)
+QUERIES = ["jtp_entropy.hip"]
+SOURCES = PLANNER + ENGINE + QUERIES + INST                # (compiled in parallel, one object each, then linked)
 INCLUDE = re.compile(rb'^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', re.M)
 
 
@@ -129,7 +131,7 @@ def build(force=False, verbose=True, extra=(), out=None, jobs=None):
         # (the template translation units take 1-2 GiB of compiler each: at most eight at once, JTP_BUILD_JOBS overrides)
         jobs = jobs or int(os.environ.get("JTP_BUILD_JOBS", 0)) or max(1, min(len(SOURCES), os.cpu_count() or 2, 8))
         with ThreadPoolExecutor(jobs) as pool:
-            objs = list(pool.map(compile_one, INST + ENGINE + PLANNER))
+            objs = list(pool.map(compile_one, INST + ENGINE + QUERIES + PLANNER))
         # link beside the target and move the result into place: a process that has the old library mapped keeps it,
         # nobody ever sees a half-written one
         tmp_out = out + ".tmp%d" % os.getpid()

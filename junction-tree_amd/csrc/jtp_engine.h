@@ -8,6 +8,7 @@
 //   jtp_map.hip        jtp_map: the most probable assignment (max-product sweep over the potentials); jtp_max_marginals: max-propagation;
 //                      jtp_map_best: the M most probable assignments
 //   jtp_joint.hip      jtp_joint: the joint of variables of different cliques, from the beliefs a propagate left
+//   jtp_entropy.hip    jtp_entropy: posterior entropy and cross-entropy against another evidence set, one streaming pass over all beliefs
 //   jtp_profile.cpp    profiling, regions, statistics;    jtp_comm.cpp   RCCL and roctx loaders, jtp_comm_*, the exchange steps
 // Every global has one definition, in the unit that owns it; the other units reach it through the functions declared here.
 #pragma once
@@ -244,6 +245,7 @@ struct jtp_plan {
     MaxMem maxm{&mem};              // jtp_max_marginals: downward and request records, work area (both knobs govern it too)
     MbestMem mbest{&mem};           // jtp_map_best: work area of one set (jtp_map's records; "map_seg" governs it too)
     JointMem joint{&mem};           // jtp_joint: records and work area
+    EntropyMem entropy{&mem};       // jtp_entropy: records and work area
     hipStream_t eval_stream = nullptr;   // stream whose kernels may still read the buffer
     bool eval_pending = false;
     int esize = 4;

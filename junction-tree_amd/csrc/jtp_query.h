@@ -1,5 +1,5 @@
-// Internal header of the query units (jtp_sample.hip, jtp_map.hip, jtp_joint.hip; jtp_engine.h includes it for the *Mem holders the
-// plan keeps by value): their records, and what the three share - how the digits of a clique's variables address its stored table
+// Internal header of the query units (jtp_sample.hip, jtp_map.hip, jtp_joint.hip, jtp_entropy.hip; jtp_engine.h includes it for the
+// *Mem holders the plan keeps by value): their records, and what they share - how the digits of a clique's variables address its stored table
 // (the one place outside the planner that knows how a compact mixed-radix row stores a variable), the walk of a lane over a block
 // of a table's index, the staging of a clique's children, the launch shape.  No function here is told which query calls it.
 #pragma once
@@ -163,6 +163,36 @@ struct JointMem {
     DeviceBuf<char> recs;
     DeviceBuf<double> work;
     explicit JointMem(MemLedger *m) : recs(m), work(m) {}
+};
+
+// jtp_entropy: one record per clique of the sampling schedule (HostPlan::sample, visit order), read by the kernels as it stands.
+// v[0, nK): the variables shared with the parent clique, host axis order, `radix` their C-order weight in k; v[nK, nK + nF): the
+// others in ASCENDING DEVICE STRIDE, the first the fastest digit of r (`radix` 1): the `lanes` lanes that share a k take r = l,
+// l + lanes, ..., so on a power-of-two layout whose low strides are F's a wave reads consecutive elements.  step[j]: digit j of
+// `lanes` in that mixed radix, what one turn of a lane adds to its counter ([step_lo, step_hi): the digits that are not zero).
+struct JtEntropy {
+    int64_t bel_off;                 // element offset of the clique's table in the belief arena
+    int64_t k_off;                   // the clique's place in a set's per-k sums (entry k)
+    int64_t part_off;                // nseg > 1: ... and in a set's segment sums (entry k * nseg + segment)
+    int32_t nK, nF;
+    uint32_t R, nk;                  // products of the cardinalities of F and of K
+    uint32_t nseg;                   // contiguous segments r is cut into, a wave each (jt_query_nseg)
+    int32_t lanes;                   // lanes that share a (k, segment): min(64, R rounded up to a power of two)
+    int32_t clique;                  // C-ABI clique number
+    int32_t step_lo, step_hi;
+    int32_t pad;
+    JtSampleVar v[JT_MAX_VARS];
+    int32_t step[JT_MAX_VARS];
+};
+// what jtp_entropy keeps with the plan: the records (built once), and grow-only the work area of one chunk of evidence sets - per
+// set the two belief arenas' addresses, per (set, clique) four words of result (t(a,a), t(a,b), S, flags), and per set the per-k
+// and the segment sums, two doubles an entry without a reference set and four with one
+struct EntropyMem {
+    DeviceBuf<JtEntropy> recs;
+    DeviceBuf<double> work;
+    int64_t entries = 0, parts = 0;  // per set: per-k entries, segment results
+    int64_t max_items = 1;           // most (k, segment) pairs x lanes of a clique
+    explicit EntropyMem(MemLedger *m) : recs(m), work(m) {}
 };
 
 // ------------------------------------------------------------------------------------------ host: records and launch shape

@@ -549,6 +549,39 @@ class Plan:
         _capi.check(rc)
         return out, int(e.value)
 
+    def entropy(self, batch_begin=0, batch_end=None, ref=None, per_clique=False):
+        """Entropy of the posterior of every evidence set in [batch_begin, batch_end), in nats, from the beliefs of the last
+        propagate (`jtp_entropy`: one streaming pass over all belief tables on the device): a float64 array (n_sets,).  `ref`: a
+        set number, or one per set of the range - the result is then (entropy, cross), `cross[i]` the cross-entropy of set
+        batch_begin + i against set ref[i]; cross - entropy is KL(set || ref), and cross is inf where the reference gives
+        probability zero to something the set does not.  `per_clique`: one more result, a float64 array (n_sets, n_cliques) of
+        the conditional entropies H(F_c | K_c) the entropy is the sum of, a column per clique in ascending order of the caller's
+        clique indices (cliques numbered 0 .. n_cliques - 1: column c is clique c).
+
+        Where sets hold a negative or NaN belief entry, or have evidence of probability zero or tables that overflowed on a plan
+        made without `scaled`, `_capi.JtpError` is raised; its `entropy`, `cross` and `clique_entropy` attributes hold the
+        arrays, NaN for those sets - the other sets are written."""
+        end = self.n_batch if batch_end is None else int(batch_end)
+        begin = int(batch_begin)
+        n_sets = max(end - begin, 0)
+        h = np.zeros(n_sets, dtype=np.float64)
+        x = refs = None
+        if ref is not None:
+            refs = np.ascontiguousarray(np.broadcast_to(np.asarray(ref, dtype=np.int32), (n_sets,)))
+            x = np.zeros(n_sets, dtype=np.float64)
+        rows = np.zeros((n_sets, self.n_cliques), dtype=np.float64) if per_clique else None
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None
+        rc = self._lib.jtp_entropy(self._handle, begin, end, ptr(refs), ptr(h), ptr(x), ptr(rows))
+        if rows is not None:                                   # (C-ABI clique number -> the caller's)
+            rows = rows[:, [self.abi_of[c] for c in sorted(self.cliques)]]
+        out = (h,) + ((x,) if x is not None else ()) + ((rows,) if per_clique else ())
+        if rc == _capi.JTP_EINVAL and n_sets > 0 and bool(np.isnan(h).any()):
+            err = _capi.JtpError(self._lib.jtp_last_error().decode("utf-8", "replace"))
+            err.entropy, err.cross, err.clique_entropy = h, x, rows
+            raise err
+        _capi.check(rc)
+        return out[0] if len(out) == 1 else out
+
     def accumulate_marginals(self, requests, weights=None, batch_begin=0, batch_end=None):
         """Expected counts (`jtp_accumulate_marginals`): for `requests` = [(clique, labels), ...] the sum over the evidence sets
         [batch_begin, batch_end) of `weights[b - batch_begin]` x the marginal `marginals(requests, batch=b)` would return, each

@@ -378,6 +378,79 @@ class JunctionTree:
             table = table / total
         return table
 
+    def _table_plan(self, memo, dtype, normalize, **extra):
+        """The cached plan with every clique table materialised (no `cover`) that the information measures run on: an entry of
+        its own per `memo`, as `sample` and `joint` keep - what `propagate(xs, changed=...)` trusts about "plan" is never said of it."""
+        import weakref
+        from . import engine
+
+        ct = self.clique_tree
+        sizes = ct.factor_graph.sizes
+        memo += "_scaled" if normalize else ""
+        mark = (dtype, tuple(sorted(extra.items())), tuple(sizes.items()), tuple(sorted(self._opts.items())))
+        hit = self._memo.get(memo)
+        plan = engine.cached_plan(hit[1], hit[2]()) if hit is not None and hit[0] == mark else None
+        if plan is None:
+            node_vars = [list(c) for c in ct.maxcliques] + [list(s) for s in self.separators]
+            if normalize:
+                extra = dict(extra, scaled=True)
+            plan, key = engine.plan_for(self.tree, node_vars, sizes, dtype, return_key=True, **extra, **self._opts)
+            self._memo[memo] = (mark, key, weakref.ref(plan))
+        return plan
+
+    def entropy(self, values, evidence=None, normalize=False):
+        """The entropy, in nats, of the distribution the factor values define - of the posterior given `evidence` ({variable:
+        observed state}) - as a float (not in the reference, which stops at marginals): H = sum over the cliques of the conditional
+        entropy of a clique's own variables given those it shares with its parent, one streaming pass over the clique beliefs on
+        the device (`engine.Plan.entropy`).  `normalize`: the propagate behind it runs on an overflow-safe plan
+        (`engine.Plan(scaled=True)`), for models whose Z lies beyond float64.  Evidence of probability zero, and factor values that
+        give a negative belief entry, raise `_capi.JtpError`.  Every clique table is materialised, as for `sample` and `joint`."""
+        return float(self.entropy_evidence_sets(values, [dict(evidence) if evidence else {}], normalize=normalize)[0])
+
+    def entropy_evidence_sets(self, values, evidence_sets, normalize=False):
+        """`entropy` for several evidence sets over the same factor values: a float64 array, one copy of the clique tables and
+        one call on the device for all sets.  A set whose evidence has probability zero raises `_capi.JtpError`, carrying
+        `entropy` (NaN for that set, the others written)."""
+        n_sets = len(evidence_sets)
+        if n_sets == 0:
+            return np.zeros(0)
+        ct = self.clique_tree
+        all_f32 = all(type(x) is np.ndarray and x.dtype == np.float32 for x in values)
+        plan = self._table_plan("plan_entropy", "f32" if all_f32 else "f64", normalize, n_batch=n_sets, share_potentials=True)
+        _stage_changed_cliques(plan, ct, values)
+        try:
+            for b, observed in enumerate(evidence_sets):
+                plan.set_evidence(dict(observed) if observed else {}, batch=b)
+            plan.propagate(sync=False)
+            return plan.entropy(0, n_sets)
+        finally:
+            for b, observed in enumerate(evidence_sets):     # (the plan is the cache's: whoever is handed it next finds no evidence set)
+                if observed:
+                    plan.set_evidence({}, batch=b)
+
+    def kl_divergence(self, values_p, values_q, evidence=None, normalize=False):
+        """KL(P || Q) in nats between the distributions two lists of factor values define over this tree's factors - between their
+        posteriors given the same `evidence` -: a float, `inf` where Q gives probability zero to something P does not.  Both value
+        lists are staged on one plan of two evidence sets, propagated, and one pass over both sets' clique beliefs forms the entropy
+        of P and its cross-entropy against Q (`engine.Plan.entropy(ref=...)`); the difference is returned, no less than 0.0."""
+        ct = self.clique_tree
+        all_f32 = all(type(x) is np.ndarray and x.dtype == np.float32 for vs in (values_p, values_q) for x in vs)
+        plan = self._table_plan("plan_kl", "f32" if all_f32 else "f64", normalize, n_batch=2)
+        factors = ct.factor_graph.factors
+        try:
+            for b, vs in enumerate((values_p, values_q)):
+                for c in range(len(ct.maxcliques)):
+                    members = [f for f, mc in enumerate(ct.factor_to_maxclique) if mc == c]
+                    plan.set_potential_product(c, [vs[f] for f in members], [list(factors[f]) for f in members], batch=b)
+                plan.set_evidence(dict(evidence) if evidence else {}, batch=b)
+            plan.propagate(sync=False)
+            h, x = plan.entropy(0, 1, ref=1)
+        finally:
+            if evidence:
+                for b in range(2):
+                    plan.set_evidence({}, batch=b)
+        return float("inf") if np.isinf(x[0]) else max(float(x[0] - h[0]), 0.0)
+
     def map(self, values, evidence=None):
         """The most probable joint assignment under the distribution the factor values define (not in the reference, which stops
         at marginals): ({variable: state}, log_value), log_value = log of the product of the factor values at that assignment -
