@@ -5,8 +5,9 @@
 //   jtp_readout.hip    beliefs, marginals, scale / Z / log Z, expected counts
 //   jtp_sample.hip     jtp_sample: joint posterior samples from the beliefs a propagate left        (these three: the queries on the sampling
 //                      schedule; jtp_query.h has their records and the table walk, child staging and launch shape they share)
-//   jtp_map.hip        jtp_map: the most probable assignment (max-product sweep over the potentials); jtp_max_marginals: max-propagation;
-//                      jtp_map_best: the M most probable assignments
+//   jtp_map.hip        jtp_map: the most probable assignment (max-product sweep over the potentials)     (these three: the max-product
+//   jtp_max.hip        jtp_max_marginals: max-propagation                                                units; jtp_maxprod.h has the work
+//   jtp_mbest.hip      jtp_map_best: the M most probable assignments                                     area and the host steps they share)
 //   jtp_joint.hip      jtp_joint: the joint of variables of different cliques, from the beliefs a propagate left
 //   jtp_entropy.hip    jtp_entropy: posterior entropy and cross-entropy against another evidence set, one streaming pass over all beliefs
 //   jtp_profile.cpp    profiling, regions, statistics;    jtp_comm.cpp   RCCL and roctx loaders, jtp_comm_*, the exchange steps

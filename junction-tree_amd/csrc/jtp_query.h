@@ -1,4 +1,5 @@
-// Internal header of the query units (jtp_sample.hip, jtp_map.hip, jtp_joint.hip, jtp_entropy.hip; jtp_engine.h includes it for the
+// Internal header of the query units (jtp_sample.hip, jtp_map.hip, jtp_max.hip, jtp_mbest.hip, jtp_joint.hip, jtp_entropy.hip - the three
+// max-product ones share more, in jtp_maxprod.h; jtp_engine.h includes it for the
 // *Mem holders the plan keeps by value): their records, and what they share - how the digits of a clique's variables address its stored table
 // (the one place outside the planner that knows how a compact mixed-radix row stores a variable), the walk of a lane over a block
 // of a table's index, the staging of a clique's children, the launch shape.  No function here is told which query calls it.

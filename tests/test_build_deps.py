@@ -54,6 +54,16 @@ def test_engine_reaches_the_face_of_the_kernels_only():
         assert FACE not in deps and not kernel_units(deps), src
 
 
+def test_max_product_units_alone_reach_their_header():
+    units = ["jtp_map.hip", "jtp_max.hip", "jtp_mbest.hip"]
+    for src in units:
+        assert src in jt_build.SOURCES
+        assert "jtp_maxprod.h" in jt_build.unit_deps(src), src
+    for src in jt_build.SOURCES:
+        if src not in units:
+            assert "jtp_maxprod.h" not in jt_build.unit_deps(src), src
+
+
 def test_planner_does_not_reach_the_engine():
     for src in jt_build.PLANNER:
         assert "jtp_engine.h" not in jt_build.unit_deps(src), src

@@ -1,5 +1,5 @@
-"""sha256 of what the three queries on the sampling schedule return (`Plan.sample`, `Plan.map`, `Plan.joint`) on the shapes their GPU
-tests use, float32 and float64, the default plan and `no_compact=True`: two builds of the library that print the same lines answer
+"""sha256 of what the queries on the sampling schedule return (`Plan.sample`, `Plan.map`, `Plan.max_marginals`, `Plan.map_best`,
+`Plan.joint`) on the shapes their GPU tests use, float32 and float64, the default plan and `no_compact=True`: two builds of the library that print the same lines answer
 these queries bit for bit alike (`JTPROP_LIB=<other build> python tools/query_digest.py` for the second column).  Needs a GPU.  The
 beliefs the samples and the joints are formed from are hashed first, so that a difference in the propagate is told from one in a query.
 
@@ -16,6 +16,7 @@ for p in ("junction-tree_amd", "oracle", "tests"):             # (as tests/conft
     sys.path.insert(0, os.path.join(ROOT, p))
 
 from junctiontree_amd import _capi, engine                    # noqa: E402
+from max_reference import factor_requests                     # noqa: E402   (the requests of the max-propagation tests)
 from test_gpu_joint import case, queries                      # noqa: E402   (the cases and the queries of the tests, "star12" among them)
 
 N_SETS = 5
@@ -48,6 +49,11 @@ def digests(name, dtype, opts):
     plan.debug_set("map_chunk", 2)
     states, log_value = plan.map()
     print("%-44s %s" % (tag + " map", sha(states, log_value)), flush=True)
+    tables, log2_scale, log_value = plan.max_marginals(factor_requests(plan))      # (every clique; the five sets in chunks of two)
+    print("%-44s %s" % (tag + " max_marginals", sha(*[t for per_set in tables for t in per_set], log2_scale, log_value)), flush=True)
+    for m in (1, 5, 16):
+        for b in (0, N_SETS - 1):                              # (the set that observes nothing, the set that observes the most)
+            print("%-44s %s" % (tag + " map_best %d set %d" % (m, b), sha(*plan.map_best(m, batch=b))), flush=True)
     if name == "root64k":
         root_vars = plan.describe()["sample"]["cliques"][0]["F"]
         asked = {"two_of_the_root": [plan.var_labels[v] for v in root_vars[:2]]}
