@@ -389,6 +389,44 @@ int jtp_max_marginals(jtp_plan *plan, int32_t batch_begin, int32_t batch_end, in
 #define JTP_MBEST_MAX 16
 int jtp_map_best(jtp_plan *plan, int32_t batch, int32_t m, int32_t *states, double *log_value, int32_t *n_found);
 
+/* Marginal MAP: the most probable assignment of the query variables M = var_ids[0 .. n_query) with every other variable summed out,
+ * m* = argmax_m sum_s prod_c psi_c(m, s), for every evidence set in [batch_begin, batch_end):
+ *     states[(b - batch_begin) * n_query + i] = state of var_ids[i] in set b (an observed query variable: its observed state)
+ *     log_value (NULL, or [batch_end - batch_begin]) = log max_m sum_s prod_c psi_c over what agrees with the set's evidence; less
+ *                 jtp_get_log_z of the set it is log P(m* | evidence).
+ * No propagate is needed, beliefs and messages are not touched; the evidence is what jtp_set_evidence last gave each set.
+ * Max and sum do not commute, so the tree the plan was made from must be STRONG for the query: with K_c the variables clique c shares
+ * with its parent clique and F_c its others, a clique whose F_c holds a variable of M has K_c inside M
+ * (junctiontree_amd.construction.strong_junction_tree builds such a tree).  The call checks exactly that, before any device work.
+ * The sweep runs over the tree as the description gave it, on the schedule of jtp_sample / jtp_map (by depth, then clique number;
+ * F_c in host axis order; children in ascending clique number).  F_c is split into FM_c = F_c n M and FS_c = F_c \ M, each in host
+ * axis order, Rm_c = prod card(FM_c), Rs_c = prod card(FS_c); rm and rs are the C-order indices over them.  Upward, deepest first,
+ * float64 throughout, only entries that agree with the evidence looked at:
+ *     U_c[k, rm] = sum over rs of ((double)psi_c[k, rm, rs] * m_1) * m_2 * ...     m_d = ldexp(raw_d[k_d], -e_d), e_d = ilogb(max raw_d)
+ *     raw_c[k]   = max over rm of U_c[k, rm]          (0 where k contradicts the evidence)
+ *     arg_c[k]   = the SMALLEST rm that attains it
+ * The sum over rs is added in an order that is a function of Rs_c alone, jtp_joint's rule: min(64, Rs_c rounded up to a power of two)
+ * lanes, lane l adds the contiguous block [l B, (l + 1) B) of rs, B = ceil(Rs_c / lanes), in ascending order, and a fixed tree of
+ * shuffles adds the lanes; from Rs_c >= 2048 on, rs is first cut into min(4096, Rs_c / 1024) contiguous segments, each summed so, and
+ * the segments' sums are added the same way (lane l those of segments l, l + 64, ...).  No floating-point atomics.  A maximum is exact,
+ * so how rm is cut ("map_seg") does not matter: equal potentials and evidence give bit-equal states and log_value whatever the plan's
+ * layout, compaction, launch flags, the chunking ("map_chunk") or any debug knob, and across repeated calls.
+ * Downward: a clique with FM_c not empty reads arg_c[k] at the digits the cliques above wrote (K_c lies in M there) and writes the
+ * digits of FM_c; a clique without FM_c writes nothing.  log_value = log(max raw_root) + ln 2 * (sum of e_c over the other cliques).
+ * So: with M = all variables every Rs_c is 1 and the call IS jtp_map - the same kernels over the same records -, bit for bit: states,
+ * ties and log_value.  With n_query = 0 it is the collect pass of sum-product, and log_value = log Z of the set.
+ * All sets of a chunk go through the same launches; a chunk is as many sets as keep the raw and arg tables (12 bytes per assignment
+ * of K_c) and the segment sums of the largest depth under 64 MiB.  The records of the last query are kept with the plan.
+ * Works where jtp_map works: plans of one set, of n_batch sets and with JTP_SHARE_POTENTIALS, float32 and float64 tables, any layout.
+ * JTP_EINVAL, before any device work: a query variable out of range, listed twice or in no clique; a bad batch range; null states
+ * with n_query > 0; a tree that is not strong for the query ("clique c maximises variable x below variable y, which is summed and
+ * shared with its parent clique p").  JTP_EUNSUPPORTED: JTP_MULTISET plans, n_ranks > 1, plans in which a clique keeps no table
+ * (cover_*).  A set FAILS as in jtp_map - an entry that agrees with its evidence is negative or NaN, or a clique's largest raw entry
+ * is zero or not finite (evidence of probability zero) -: its states are all -1, its log_value -inf; every set of the range is still
+ * written, the call returns JTP_EINVAL and the message names the number of failed sets and the first. */
+int jtp_marginal_map(jtp_plan *plan, int32_t batch_begin, int32_t batch_end, int32_t n_query, const int32_t *var_ids, int32_t *states,
+                     double *log_value);
+
 /* The joint of n_query distinct variables that need not share a clique, from the beliefs of the last propagate of evidence set
  * `batch`: host[] = the table over var_ids[0 .. n_query) in that axis order (doubles, C order).  Unnormalised in the sense of
  * jtp_get_marginal: it sums to Z, and on a JTP_SCALED plan it is the true table times 2^-E, E the exponent of the TOP clique below

@@ -21,7 +21,7 @@ ENGINE = ["jtp_engine.hip", "jtp_upload.hip", "jtp_propagate.hip", "jtp_readout.
 # (the planner's units, pure host C++: csrc/jtp_plan_build.h has the map)
 PLANNER = ["jtp_plan.cpp", "jtp_plan_layout.cpp", "jtp_plan_loops.cpp", "jtp_plan_tasks.cpp", "jtp_plan_schedule.cpp", "jtp_plan_json.cpp"]
 # (query units added since the engine's list was fixed at nine: csrc/jtp_query.h has their records)
-QUERIES = ["jtp_mbest.hip", "jtp_max.hip", "jtp_entropy.hip"]
+QUERIES = ["jtp_mbest.hip", "jtp_max.hip", "jtp_entropy.hip", "jtp_mmap.hip"]
 SOURCES = PLANNER + ENGINE + QUERIES + INST                # (compiled in parallel, one object each, then linked)
 INCLUDE = re.compile(rb'^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', re.M)
 

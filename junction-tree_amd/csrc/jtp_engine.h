@@ -8,6 +8,8 @@
 //   jtp_map.hip        jtp_map: the most probable assignment (max-product sweep over the potentials)     (these three: the max-product
 //   jtp_max.hip        jtp_max_marginals: max-propagation                                                units; jtp_maxprod.h has the work
 //   jtp_mbest.hip      jtp_map_best: the M most probable assignments                                     area and the host steps they share)
+//   jtp_mmap.hip       jtp_marginal_map: the most probable assignment of some variables, the others summed (jtp_sweep.h: the upward
+//                      sweep's work area and host steps, which it shares with the three above; jtp_map's kernels, and its own)
 //   jtp_joint.hip      jtp_joint: the joint of variables of different cliques, from the beliefs a propagate left
 //   jtp_entropy.hip    jtp_entropy: posterior entropy and cross-entropy against another evidence set, one streaming pass over all beliefs
 //   jtp_profile.cpp    profiling, regions, statistics;    jtp_comm.cpp   RCCL and roctx loaders, jtp_comm_*, the exchange steps
@@ -245,6 +247,7 @@ struct jtp_plan {
     int64_t map_seg = 0;            // jtp_debug_set "map_seg": entries per segment of r (0: JT_QUERY_SEG); setting it drops the records
     MaxMem maxm{&mem};              // jtp_max_marginals: downward and request records, work area (both knobs govern it too)
     MbestMem mbest{&mem};           // jtp_map_best: work area of one set (jtp_map's records; "map_seg" governs it too)
+    MmapMem mmap{&mem};             // jtp_marginal_map: the records of the last query and the work area (both knobs govern it too)
     JointMem joint{&mem};           // jtp_joint: records and work area
     EntropyMem entropy{&mem};       // jtp_entropy: records and work area
     hipStream_t eval_stream = nullptr;   // stream whose kernels may still read the buffer

@@ -1,5 +1,6 @@
 // The most probable joint assignment on the device (jtp_map: an upward sweep over the clique potentials and a decode), and the host
-// steps the three max-product units share (jtp_maxprod.h declares them; jtp_max.hip and jtp_mbest.hip are the other two).
+// steps the three max-product units share (jtp_maxprod.h and jtp_sweep.h declare them; jtp_max.hip and jtp_mbest.hip are the other two;
+// jtp_mmap.hip takes those of jtp_sweep.h).
 #include "jtp_maxprod.h"
 
 // jtp_map works on the sampling schedule (HostPlan::sample: the caller's tree by depth, then clique number; K the variables a clique
@@ -18,24 +19,7 @@
 // A set fails where an entry that agrees with its evidence is negative or NaN, or where a clique's maximum is zero or not finite
 // (the root's then is): its states are -1.
 
-// the wave's (largest w, smallest r among equals), in every lane: six shuffle steps
-__device__ __forceinline__ void jt_map_wave_best(double &best, uint32_t &best_r) {
-    for (int d = 32; d >= 1; d >>= 1) {
-        const double ow = __shfl_xor(best, d, 64);
-        const uint32_t orr = __shfl_xor(best_r, d, 64);
-        if (ow > best || (ow == best && orr < best_r)) best = ow, best_r = orr;
-    }
-}
-
-// lane 0 of a wave: raw_c[k], arg_c[k] and the clique's running maximum
-__device__ __forceinline__ void jt_map_store(const JtMap &rec, const JtMapWork &wk, int set, uint32_t k, double best, uint32_t best_r, int n_rec, int64_t entries) {
-    if (!(best >= 0.0)) best = 0.0, best_r = 0;          // (nothing looked at: k contradicts the evidence)
-    best = fabs(best);                                   // (-0.0: its bit pattern would be the largest of all)
-    const int64_t p = (int64_t)set * entries + rec.raw_off + k;
-    wk.raw[p] = best;
-    wk.arg[p] = best_r;
-    jt_maxprod_keep_top(wk.top + (int64_t)set * n_rec + rec.ord, best);
-}
+// (jt_map_wave_best, the wave's (largest w, smallest r among equals), and jt_map_store, what lane 0 writes: jtp_sweep.h)
 
 template <typename T>
 __global__ __launch_bounds__(256) void jt_map_collect_level(const JtMap *__restrict__ recs, const JtMapChild *__restrict__ kids, JtMapWork wk,
@@ -309,9 +293,21 @@ int maxprod_stage_sets(jtp_plan *pl, size_t first, size_t cnt, std::vector<const
 void map_upward_sweep(const HostPlan &hp, const MapMem &up, const JtMapWork &wk, size_t cnt, hipStream_t s) {
     const int n_vars = hp.n_vars, n_rec = (int)hp.sample.size();
     maxprod_upward(hp, up, cnt, [&](const JtMap *recs, dim3 grid, dim3 mgrid, bool merge) {
-        JT_QUERY_LAUNCH(hp.dtype, jt_map_collect_level, grid, s, recs, up.kids.get(), wk, n_vars, n_rec, (int)cnt, (int64_t)up.entries, (int64_t)up.parts);
-        if (merge) hipLaunchKernelGGL(jt_map_merge, mgrid, dim3(256), 0, s, recs, wk, n_rec, (int)cnt, (int64_t)up.entries, (int64_t)up.parts);
+        map_collect_launch(hp.dtype, recs, up.kids.get(), wk, grid, n_vars, n_rec, (int)cnt, (int64_t)up.entries, (int64_t)up.parts, s);
+        if (merge) map_merge_launch(recs, wk, mgrid, n_rec, (int)cnt, (int64_t)up.entries, (int64_t)up.parts, s);
     });
+}
+
+void map_collect_launch(int dtype, const JtMap *recs, const JtMapChild *kids, const JtMapWork &wk, dim3 grid, int n_vars, int n_rec, int cnt, int64_t entries, int64_t parts, hipStream_t s) {
+    JT_QUERY_LAUNCH(dtype, jt_map_collect_level, grid, s, recs, kids, wk, n_vars, n_rec, cnt, entries, parts);
+}
+
+void map_merge_launch(const JtMap *recs, const JtMapWork &wk, dim3 mgrid, int n_rec, int cnt, int64_t entries, int64_t parts, hipStream_t s) {
+    hipLaunchKernelGGL(jt_map_merge, mgrid, dim3(256), 0, s, recs, wk, n_rec, cnt, entries, parts);
+}
+
+void map_decode_launch(const JtMap *recs, const int32_t *depth_begin, int n_depths, const JtMapWork &wk, size_t cnt, int n_vars, int n_rec, int64_t entries, hipStream_t s) {
+    hipLaunchKernelGGL(jt_map_decode, dim3((unsigned)cnt), dim3(256), 0, s, recs, depth_begin, n_depths, wk, n_vars, n_rec, entries);
 }
 
 MaxprodValue maxprod_value(const unsigned long long *top, size_t n_rec, bool flagged) {
@@ -369,8 +365,7 @@ extern "C" int jtp_map(jtp_plan *pl, int32_t batch_begin, int32_t batch_end, int
         if ((rc = maxprod_stage_sets(pl, (size_t)batch_begin + at, cnt, psi, ev, wk.psi, wk.ev, wk.top, wk.flag, s))) return rc;
         if (n_vars) HIP_TRY(hipMemsetAsync(wk.states, 0, cnt * n_vars * sizeof(int32_t), s));      // (a variable of no clique stays 0)
         map_upward_sweep(hp, mm, wk, cnt, s);
-        hipLaunchKernelGGL(jt_map_decode, dim3((unsigned)cnt), dim3(256), 0, s, mm.recs.get(), mm.depth_begin.get(), (int)hp.sample_depths.size(), wk, (int)n_vars, (int)n_rec,
-                           (int64_t)entries);
+        map_decode_launch(mm.recs.get(), mm.depth_begin.get(), (int)hp.sample_depths.size(), wk, cnt, (int)n_vars, (int)n_rec, (int64_t)entries, s);
         HIP_TRY(hipGetLastError());
         if (n_vars) HIP_TRY(hipMemcpyAsync(states + at * n_vars, wk.states, cnt * n_vars * sizeof(int32_t), hipMemcpyDeviceToHost, s));
         HIP_TRY(hipMemcpyAsync(top.data(), wk.top, cnt * n_rec * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));

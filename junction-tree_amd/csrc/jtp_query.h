@@ -79,6 +79,38 @@ struct MapMem {
     explicit MapMem(MemLedger *m) : recs(m), kids(m), depth_begin(m), work(m) {}
 };
 
+// jtp_marginal_map: the records of a query, read by jtp_map's kernels and by jt_mmap_level.  A record is a JtMap whose F is cut in
+// two - v[0, nK): K; v[nK, nK + nF): FM, the clique's own variables that are maximised, `radix` their weight in rm (R = Rm, nseg its
+// segments); v[nK + nF, nK + nF + nS): FS, those that are summed, `radix` their weight in rs - with a JtMmapExt beside it.  Inside a
+// depth the cliques with Rs = 1 come first: jtp_map's kernels take those as they stand.  A child's stride[] covers all three parts.
+struct JtMmapExt {
+    int64_t spart_off;               // sseg > 1: the clique's place in a set's segment sums of its depth (entry (k * Rm + rm) * sseg + segment)
+    int32_t nS;
+    int32_t lanes;                   // lanes that share one (k, rm): min(64, Rs rounded up to a power of two)
+    uint32_t Rs;                     // product of the cardinalities of FS
+    uint32_t sseg;                   // contiguous segments the sum over rs is cut into, a wave each (jt_query_nseg of Rs alone)
+};
+// what jtp_marginal_map keeps with the plan: the records of the last query (`key`: the entries per segment of rm they were cut by,
+// then the query sorted) and grow-only the work area of one chunk of evidence sets - jtp_map's (map_work), then the segment sums
+struct MmapMem {
+    struct Depth {
+        int32_t a0 = 0, a1 = 0, b1 = 0;  // records [a0, a1): Rs = 1; [a1, b1): the others
+        int64_t items_a = 0, items_b = 0;    // most waves of work a set gives a clique in jt_map_collect_level, in jt_mmap_level
+        int64_t items_s = 0;             // ... and in jt_mmap_merge (0: no sum of the depth is cut)
+        char merge = 0;                  // some clique's rm is cut into segments: jt_map_merge
+    };
+    DeviceBuf<JtMap> recs;
+    DeviceBuf<JtMmapExt> ext;
+    DeviceBuf<JtMapChild> kids;
+    DeviceBuf<int32_t> depth_begin;
+    DeviceBuf<char> work;
+    std::vector<int32_t> key;
+    int64_t entries = 0, parts = 0;      // per set: raw / arg entries, segment results of rm
+    int64_t sparts = 0;                  // per set: segment sums of the depth that has most
+    std::vector<Depth> depths;
+    explicit MmapMem(MemLedger *m) : recs(m), ext(m), kids(m), depth_begin(m), work(m) {}
+};
+
 // jtp_max_marginals: one record per table the downward half of max-propagation forms by a maximum over a clique c's entries - the
 // downward message to a child d of c (one per clique but the root, in the visit order of d) and a request (clique c, variables V).
 // v[0, nK): the variables of the output - K_d with the weights raw_d has, or V in the requested order, C order -; v[nK, nK + nF):

@@ -18,7 +18,7 @@ Everything is iterative (no recursion limits on long chains).
 
 from itertools import combinations
 
-__all__ = ["triangulate", "find_triangulation", "construct_junction_tree", "nest_tree"]
+__all__ = ["triangulate", "find_triangulation", "construct_junction_tree", "nest_tree", "strong_junction_tree", "is_strong"]
 
 
 def _first_seen_order(factors, sizes):
@@ -141,6 +141,110 @@ def nest_tree(parent, children, sep_of):
     for c in reversed(order):
         sub[c] = [c] + [(sep_of[k], sub[k]) for k in children[c]]
     return sub[root]
+
+
+def strong_junction_tree(factors, sizes, last):
+    """A junction tree for marginal MAP over the variables `last` (`JunctionTree.marginal_map`): every variable outside
+    `last` is eliminated before any variable of `last`, each group by greedy min-fill among its own (the cost of `triangulate`),
+    and the tree is the ELIMINATION tree, not a maximum-weight spanning tree - the clique made when v is eliminated hangs under the
+    clique of the earliest-eliminated of v's remaining neighbours; a clique contained in a child is merged into it.  The root is
+    the clique of the last eliminated variable, other components hang under it with empty separators.  Such a tree is strong
+    (`is_strong`): a sweep towards the root may sum a clique's own variables before it maximises, clique by clique.
+    Returns (maxcliques, factor_to_maxclique, tree, separators) in the formats of `triangulate` and `construct_junction_tree`.
+    The width can be far above that of the unconstrained tree: that is inherent to marginal MAP."""
+    last = set(last)
+    rank = _first_seen_order(factors, sizes)
+    adj = {v: set() for v in rank}
+    for f in factors:
+        for a, b in combinations(f, 2):
+            if a != b:
+                adj[a].add(b)
+                adj[b].add(a)
+
+    def cost_of(v):
+        nb = adj[v]
+        missing = sum(len(nb) - 1 - len(adj[a] & nb) for a in nb) // 2
+        w = sizes[v]
+        for a in nb:
+            w *= sizes[a]
+        return (missing, w, rank[v])
+
+    order, clique_of, nbrs_at = [], {}, {}
+    for group in ([v for v in rank if v not in last], [v for v in rank if v in last]):
+        pending = set(group)
+        cost = {v: cost_of(v) for v in pending}
+        while pending:
+            v = min(pending, key=cost.__getitem__)
+            nb = adj[v]
+            clique_of[v] = {v} | nb
+            nbrs_at[v] = set(nb)
+            touched = set(nb)
+            for a, b in combinations(nb, 2):
+                if b not in adj[a]:
+                    adj[a].add(b)
+                    adj[b].add(a)
+            for a in nb:
+                adj[a].discard(v)
+                touched |= adj[a]
+            pending.discard(v)
+            del adj[v]
+            order.append(v)
+            for u in touched:
+                if u in pending:
+                    cost[u] = cost_of(u)
+    when = {v: t for t, v in enumerate(order)}
+    up = {v: (min(nbrs_at[v], key=when.__getitem__) if nbrs_at[v] else None) for v in order}
+    # a clique contained in a child is merged into (the first such) child; chains of them end in the child that survives
+    into = {}
+    for v in order:
+        u = up[v]
+        if u is not None and u not in into and clique_of[u] <= clique_of[v]:
+            into[u] = v
+
+    def survivor(v):
+        while v in into:
+            v = into[v]
+        return v
+
+    kept = [v for v in reversed(order) if v not in into]            # (the root's first)
+    number = {v: i for i, v in enumerate(kept)}
+    n = len(kept)
+    parent = [-1] * n
+    root = number[survivor(order[-1])] if order else None
+    for v in kept:
+        t = v
+        while up[t] is not None and into.get(up[t]) == t:           # (the top of the chain merged into v)
+            t = up[t]
+        if up[t] is not None:
+            parent[number[v]] = number[survivor(up[t])]
+        elif number[v] != root:
+            parent[number[v]] = root                                # (another component: an empty separator)
+    maxcliques = [sorted(clique_of[v], key=rank.__getitem__) for v in kept]
+    sets = [clique_of[v] for v in kept]
+    children = [[] for _ in range(n)]
+    sep_of, separators = {}, []
+    for c in range(n):
+        if parent[c] >= 0:
+            children[parent[c]].append(c)
+            sep_of[c] = n + len(separators)
+            separators.append([x for x in maxcliques[c] if x in sets[parent[c]]])
+    factor_to_maxclique = [number[survivor(min(f, key=when.__getitem__))] if f else 0 for f in factors]
+    tree = nest_tree(parent, children, sep_of) if n else []
+    return maxcliques, factor_to_maxclique, tree, separators
+
+
+def is_strong(parent, node_vars, last):
+    """Whether the rooted tree (`parent[c]`: the parent clique of clique c, -1 for the root; `node_vars[c]`: its variables) is strong
+    for the variables `last`: along every edge, with K_c the variables clique c shares with its parent and F_c its others, if F_c
+    holds a variable of `last` then K_c lies inside `last`.  Exactly what `jtp_marginal_map` asks of a plan's tree."""
+    last = set(last)
+    for c, p in enumerate(parent):
+        if p < 0:
+            continue
+        shared = set(node_vars[c]) & set(node_vars[p])
+        if (set(node_vars[c]) - shared) & last and not shared <= last:
+            return False
+    return True
 
 
 def construct_junction_tree(cliques, sizes):

@@ -482,6 +482,47 @@ class Plan:
         _capi.check(rc)
         return states[:found.value], value[:found.value]
 
+    def marginal_map(self, variables, batch_begin=0, batch_end=None):
+        """Marginal MAP of every evidence set in [batch_begin, batch_end) (`jtp_marginal_map`): the most probable assignment of
+        `variables` with every other variable summed out - an int32 array (n_sets, len(variables)), column i the state of
+        `variables[i]`, and a float64 array (n_sets,) of log max_m sum_s prod psi; less `log_z(batch)[1]` it is log P(m* | evidence).
+        A sweep over the staged potentials that sums a clique's own summed variables, then maximises over its query variables: no
+        propagate is needed, and what one left is not touched.  The plan's tree must be strong for the query
+        (`construction.strong_junction_tree`, `construction.is_strong`): ValueError otherwise.  With every variable in the query it
+        is `map`, bit for bit; with none, `log_value` is log Z.  Equal potentials and evidence give bit-equal results whatever the
+        plan's layout.
+
+        Where sets have no assignment of positive finite value `_capi.JtpError` is raised, as `map` raises it; its `states` and
+        `log_value` attributes hold the arrays, with -1 and -inf for those sets."""
+        variables = list(variables)
+        unknown = [lab for lab in variables if lab not in self.var_id and lab not in self._trivial]
+        if unknown:
+            raise ValueError("variable %r is in no clique of the plan" % (unknown[0],))
+        if len(set(variables)) != len(variables):
+            raise ValueError("a variable is listed twice: %r" % (variables,))
+        end = self.n_batch if batch_end is None else int(batch_end)
+        begin = int(batch_begin)
+        n_sets = max(end - begin, 0)
+        on_device = [i for i, lab in enumerate(variables) if lab not in self._trivial]
+        ids = np.array([self.var_id[variables[i]] for i in on_device] + [0], dtype=np.int32)      # (one past the end: never an empty array)
+        got = np.zeros((n_sets, len(on_device)), dtype=np.int32)
+        value = np.zeros(n_sets, dtype=np.float64)
+        rc = self._lib.jtp_marginal_map(self._handle, begin, end, len(on_device), ids.ctypes.data_as(C.c_void_p), got.ctypes.data_as(C.c_void_p),
+                                        value.ctypes.data_as(C.c_void_p))
+        failed = rc == _capi.JTP_EINVAL and n_sets > 0 and bool(np.isneginf(value).any())
+        if rc != _capi.JTP_OK and not failed:
+            _capi.check(rc)
+        states = got
+        if len(on_device) != len(variables):                 # (one-state variables the plan keeps on the host: state 0)
+            states = np.zeros((n_sets, len(variables)), dtype=np.int32)
+            states[np.isneginf(value)] = -1
+            states[:, on_device] = got
+        if failed:
+            err = _capi.JtpError(self._lib.jtp_last_error().decode("utf-8", "replace"))
+            err.states, err.log_value = states, value
+            raise err
+        return states, value
+
     def max_marginals(self, requests, batch_begin=0, batch_end=None):
         """Max-propagation (`jtp_max_marginals`): for `requests` = [(clique, labels), ...] and every evidence set in [batch_begin,
         batch_end) the max-marginal of the clique onto `labels` - per assignment of those variables, the value of the best full

@@ -505,6 +505,68 @@ class JunctionTree:
 
         return self._on_map_plan(values, [dict(evidence) if evidence else {}], sweep)
 
+    def marginal_map(self, values, variables, evidence=None):
+        """Marginal MAP (not in the reference): the most probable assignment of `variables` with every other variable summed out,
+        ({variable: state} for those variables only, log_value) - log_value = log max_m sum_s prod of the factor values; less log Z
+        it is the log posterior probability of that assignment.  `evidence`: {variable: observed state}.  `map` maximises over the
+        other variables instead of summing them, which is another answer in general.  See `marginal_map_evidence_sets`."""
+        states, value = self.marginal_map_evidence_sets(values, variables, [dict(evidence) if evidence else {}])
+        return {lab: int(col[0]) for lab, col in states.items()}, float(value[0])
+
+    def marginal_map_evidence_sets(self, values, variables, evidence_sets):
+        """`marginal_map` for several evidence sets over the same factor values: ({variable: int32 array of length n_sets}, float64
+        array of the sets' log values), all sets through the same launches of one sweep on the device (`engine.Plan.marginal_map`).
+
+        Max and sum do not commute, so the sweep does not run on this tree but on a strong junction tree of the same factors
+        built for the query (`construction.strong_junction_tree`: the summed variables eliminated first), remembered per set of
+        query variables; the factor values apply to it as they are.  Its cliques can be far wider than this tree's - that is
+        inherent to marginal MAP - and a clique beyond the engine's limits raises `_capi.UnsupportedStructure`.  Every clique
+        table is materialised, as for `map`.  An empty query gives ({}, log Z).  A set whose evidence has probability zero raises
+        `_capi.JtpError`, carrying `states` (-1 for that set) and `log_value` (-inf)."""
+        from ._capi import UnsupportedStructure
+
+        fg = self.clique_tree.factor_graph
+        sizes = fg.sizes
+        variables = list(variables)
+        for lab in variables:
+            if lab not in sizes:
+                raise ValueError("variable %r is not a variable of the model" % (lab,))
+        if len(set(variables)) != len(variables):
+            raise ValueError("a variable is listed twice: %r" % (variables,))
+        n_sets = len(evidence_sets)
+        if n_sets == 0:
+            return {lab: np.zeros(0, dtype=np.int32) for lab in variables}, np.zeros(0)
+        memo = ("strong", frozenset(variables))
+        mark = (tuple(sizes.items()), tuple(sorted(self._opts.items())))
+        hit = self._memo.get(memo)
+        if hit is None or hit[0] != mark:
+            maxcliques, f2m, tree, separators = cons.strong_junction_tree(fg.factors, sizes, variables)
+            strong = JunctionTree(tree=tree, separators=separators,
+                                  clique_tree=CliqueGraph(maxcliques=maxcliques, factor_to_maxclique=f2m, factor_graph=fg), _opts=dict(self._opts))
+            hit = self._memo[memo] = (mark, strong)
+        strong = hit[1]
+
+        def columns(known, states, value):
+            got = dict(zip(known, states.T))
+            rest = np.where(np.isneginf(value), -1, 0).astype(np.int32)     # (a variable of no factor has no state to choose: 0)
+            return {lab: got.get(lab, rest) for lab in variables}
+
+        def sweep(plan):
+            known = [lab for lab in variables if lab in plan.var_id or lab in plan._trivial]
+            try:
+                states, value = plan.marginal_map(known, 0, n_sets)
+            except Exception as exc:
+                if hasattr(exc, "states"):
+                    exc.states = columns(known, exc.states, exc.log_value)
+                raise
+            return columns(known, states, value), value
+
+        try:
+            return strong._on_map_plan(values, evidence_sets, sweep)
+        except UnsupportedStructure as exc:
+            raise UnsupportedStructure("%s - marginal MAP runs on a junction tree in which the summed variables are eliminated before the query variables, "
+                                       "whose cliques can be far larger than those of the tree `propagate` uses" % exc) from exc
+
     def _on_map_plan(self, values, evidence_sets, sweep):
         """`sweep(plan)` on the plan the max-product calls share (`map_evidence_sets`, `max_propagate_evidence_sets`): one copy of the
         clique tables, an evidence set per entry of the non-empty `evidence_sets`; the factor values staged, the evidence set, and
