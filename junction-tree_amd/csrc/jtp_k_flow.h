@@ -37,6 +37,37 @@ __global__ __launch_bounds__(JT_THREADS, JT_FLOW_WAVES) void jt_collect_flow(con
     }
 }
 
+// jt_collect_flow with KEEP = true: the row loads carry the workgroup's cache policy (JtTask::keep_rows).  The collect launch of plans
+// that keep rows and launch their phases separately (a rank's share of a tree): the distribute launch - jt_propagate_flow - finds in
+// the Infinity Cache what this one left there.  A kernel of its own: chains and plans that keep nothing run jt_collect_flow, whose row
+// loop has no choice to make.
+template <typename T>
+__global__ __launch_bounds__(JT_THREADS, JT_FLOW_WAVES) void jt_collect_flow_keep(const JtTask *__restrict__ tasks,
+                                                                   const JtBlock *__restrict__ blk, const int *__restrict__ itab,
+                                                                   const T *__restrict__ psi, T *__restrict__ bel,
+                                                                   double *__restrict__ msg, JtFlow fl) {
+    __shared__ uint32_t flow_ctl[JT_CTL_WORDS];
+    const uint64_t t_entry = __builtin_amdgcn_s_memrealtime();
+    const uint32_t ticket = jt_flow_ticket(fl, flow_ctl);
+    const JtBlock &bk = blk[ticket];
+    if (jt_lean_block<T>(bk, itab, msg, fl, flow_ctl)) return;
+    const JtTask &tk = tasks[bk.task];
+    if (tk.kind != 0) {
+        jt_reduce<true>(tk, bk, msg, fl);
+        return;
+    }
+    if (tk.unit) {
+        jt_unit_collect<T, true, false>(tk, bk, itab, psi, bel, msg, fl, ticket, flow_ctl, t_entry);
+        return;
+    }
+    switch (tk.n_in) {
+        case 0: jt_pass<T, 0, 1, 0, true, true, false, true>(tk, bk, itab, psi, bel, msg, fl, ticket, flow_ctl, t_entry); break;
+        case 1: jt_pass<T, 1, 1, 0, true, true, false, true>(tk, bk, itab, psi, bel, msg, fl, ticket, flow_ctl, t_entry); break;
+        case 2: jt_pass<T, 2, 1, 0, true, true, false, true>(tk, bk, itab, psi, bel, msg, fl, ticket, flow_ctl, t_entry); break;
+        default: jt_pass<T, 3, 1, 0, true, true, false, true>(tk, bk, itab, psi, bel, msg, fl, ticket, flow_ctl, t_entry); break;
+    }
+}
+
 template <typename T, bool EARLY = false>
 __device__ __forceinline__ void jt_distribute_flow_body(const JtTask *__restrict__ tasks, const JtBlock *__restrict__ blk,
                                                         const int *__restrict__ itab, const T *__restrict__ psi, T *__restrict__ bel,

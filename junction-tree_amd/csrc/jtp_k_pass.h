@@ -154,9 +154,11 @@ __device__ __forceinline__ void jt_pass(const JtTask &tk, const JtBlock &bk, con
     // zero row; their belief stores go to the row behind it (jtp_internal.h).  The whole chunk may be such.
     const T *zero_row = psi_arena + (uint32_t)tid * VEC;
     const bool chunk_ok = !(bk.flags & JT_BLOCK_INVALID);
-    // (uniform) default cache policy for the first table rows, see JtTask::keep_rows.  KEEP: only the kernel that runs both phases
-    // in one launch looks at the flag (jt_propagate_flow: the plans with a top that both passes visit close together in time) -
-    // the uniform branch around the two forms of the load cost config 2's chain kernels 1.5 % for nothing
+    // (uniform) default cache policy for this workgroup's table rows, see JtTask::keep_rows.  KEEP: only the kernel that runs both
+    // phases in one launch looks at the flag (jt_propagate_flow: the plans with levels that both passes visit close together in
+    // time) - in every kernel, the uniform branch around the two forms of the FIRST loads cost config 2's chain kernels 1.5 % for
+    // nothing, around the refills in the row loop 3.5 % (round 4).  The distribute pass's read of a kept row is its last use and
+    // still takes the default policy: read non-temporally it was slower at every budget (docs/EXPERIMENTS.md, "Cache residency")
     const bool keep_rows = KEEP && (bk.flags & JT_BLOCK_KEEP_ROWS) != 0;
     const uint32_t ring_lds = (uint32_t)(uintptr_t)((__attribute__((address_space(3))) char *)smem) + (uint32_t)wave * (U * 1024);
     const char *ring = smem + wave * (U * 1024) + lane * 16;
@@ -625,11 +627,15 @@ __device__ __forceinline__ void jt_pass(const JtTask &tk, const JtBlock &bk, con
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             const int inext = (i + U < total) ? i + U : total - 1;
             const uint32_t xnext = (uint32_t)__builtin_amdgcn_readlane(trow[0], inext);
-            // (always non-temporal here: JtTask::keep_rows is honoured by the FIRST loads only - a choice of cache policy in
-            //  this loop, a uniform branch around two forms of the load, cost config 2 3.5 % whichever way it went; the workgroups
-            //  of the levels nearest the root have four rows - all of them first loads)
-            jt_dma16((xnext == JT_NO_ROW || !chunk_ok) ? zero_row : psi + (xF + xnext),
-                     __builtin_amdgcn_readfirstlane(ring_lds + SLOT * 1024));
+            // (KEEP builds: the refill carries the workgroup's policy like the first loads - a kept level's workgroups have 8-16 rows,
+            //  and a row loaded non-temporally is a row the other pass fetches from HBM.  Every other build: always non-temporal, no
+            //  choice in this loop - the 3.5 % of the note at `keep_rows` above)
+            if constexpr (KEEP)
+                jt_dma16((xnext == JT_NO_ROW || !chunk_ok) ? zero_row : psi + (xF + xnext),
+                         __builtin_amdgcn_readfirstlane(ring_lds + SLOT * 1024), keep_rows);
+            else
+                jt_dma16((xnext == JT_NO_ROW || !chunk_ok) ? zero_row : psi + (xF + xnext),
+                         __builtin_amdgcn_readfirstlane(ring_lds + SLOT * 1024));
         }
         }
         // (compact mixed-radix rows: the second group's last step may have no row - an odd number of rows)

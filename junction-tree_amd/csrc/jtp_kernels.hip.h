@@ -37,6 +37,7 @@ template <typename T> __global__ void jt_lean_single(JT_KARGS(T));
 template <typename T> __global__ void jt_marginals(JT_KARGS(T));
 // families flow, both and bothm (jtp_k_flow.h)
 template <typename T> __global__ void jt_collect_flow(JT_KARGS(T));
+template <typename T> __global__ void jt_collect_flow_keep(JT_KARGS(T));
 template <typename T> __global__ void jt_propagate_flow(JT_KARGS(T));
 template <typename T> __global__ void jt_propagate_flow_marg(JT_KARGS(T));
 template <typename T> __global__ void jt_distribute_flow(JT_KARGS(T));
@@ -59,6 +60,7 @@ template <typename T, int HASP, int NCH> __global__ void jt_distribute(JT_KARGS(
 // one translation unit with everything took 3.5 minutes to compile.  X = `extern` or nothing.
 #define JT_INST_FLOW(X, T)                                                   \
     X template __global__ void jt_collect_flow<T>(JT_KARGS(T));              \
+    X template __global__ void jt_collect_flow_keep<T>(JT_KARGS(T));         \
     X template __global__ void jt_distribute_flow<T>(JT_KARGS(T));           \
     X template __global__ void jt_distribute_flow_chain<T>(JT_KARGS(T));
 #define JT_INST_LEVEL(X, T)                                                  \

@@ -44,7 +44,9 @@ PlanKnobs jtp_read_knobs() {
     k.top_share = getd("JTP_TOP_SHARE", 0.12);
     k.top_rows2 = getd("JTP_TOP_ROWS2", 2048.0);
     k.top_loop2 = geti("JTP_TOP_LOOP2", 2);
-    k.keep_rows_mb = getd("JTP_KEEP_ROWS_MB", 128.0);
+    k.keep_rows_mb = getd("JTP_KEEP_ROWS_MB", k.keep_rows_mb);
+    k.keep_top = geti("JTP_KEEP_TOP", k.keep_top);
+    k.keep_bw = getd("JTP_KEEP_BW", k.keep_bw);
     k.esum_always = geti("JTP_EXPERIMENT_ESUM_ALWAYS", 0);
     k.marg_group = std::max(1, std::min(geti("JTP_MARG_GROUP", JT_MAX_OUT), JT_MAX_OUT));
     k.marg_block_log2 = geti("JTP_MARG_BLOCK_LOG2", 0);

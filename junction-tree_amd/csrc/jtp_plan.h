@@ -171,7 +171,9 @@ struct PlanKnobs {
     int no_tsplit = 0;                                              // JTP_NO_TSPLIT: no variable across bit TB in a clique with mixed-radix rows (the first form of round 3)
     double tmix_fill = 0.6;                                         // JTP_TMIX_FILL: mixed-radix rows for cliques whose bit-field thread part would be emptier than this
     int esum_always = 0;                                            // JTP_EXPERIMENT_ESUM_ALWAYS: multi-set tasks keep summing a vector's elements first whatever the evidence (timing experiment, wrong results)
-    double keep_rows_mb = 128.0;                                      // JTP_KEEP_ROWS_MB: table rows of the levels nearest the root, up to this many MiB, are loaded with the default cache policy (0: all non-temporal; A/B on one box: config 4 0.6037 -> 0.5990 ms, an 8-rank share of it 198.5 -> 195.4 us)
+    double keep_rows_mb = 192.0;                                      // JTP_KEEP_ROWS_MB: the tables of whole tree levels, up to this many MiB per rank, are loaded with the default cache policy by both passes (JtTask::keep_rows; 0: all non-temporal).  Sweep on one box, config 4, parent commit 0.6000-0.6004 ms: 128 (level 4 + the narrow top) 0.6008-0.6012, 192 (levels 4 and 5) 0.5876-0.5884, 224 0.5871-0.5874, 256 (252 MiB kept) 0.6007 - profiles/keep_rows_sweep.txt
+    int keep_top = 1;                                               // JTP_KEEP_TOP: the narrow levels nearest the root take the budget the bandwidth-bound ones leave
+    double keep_bw = 0.0;                                           // JTP_KEEP_BW: the streaming rate in bytes/us a level's bytes are priced at (0: the cost model's, JTP_COST_BW)
     int no_ef_share = 0;                                            // JTP_NO_EF_SHARE: multi-set plans compute every set's upward messages (round 4), no evidence-free group to copy from
     int unit_joint_down = 0;                                        // JTP_UNIT_JOINT_DOWN: a unit clique forms its downward messages in ONE mode-1 pass (the first form of round 5) instead of a task each
     int no_vgroups = 0;                                             // JTP_NO_VGROUPS: mixed-radix rows keep one row per step (round 3)
@@ -262,6 +264,10 @@ struct HostPlan {
     bool multiset = false;
     double staging_bytes = 0;        // message bytes all workgroups load while staging (partial copies included)
     double table_bytes = 0;          // clique-table bytes all workgroups stream (reads + belief writes)
+    // JtTask::keep_rows, as schedule() chose: the budget in bytes (0: nothing is kept), the table bytes this rank's collect and
+    // distribute passes load with the default cache policy, the tree levels they belong to
+    double keep_budget = 0, keep_bytes[2] = {0, 0};
+    std::vector<int> keep_levels;
     int n_messages = 0;
     std::vector<SampleClique> sample;            // sampling schedule, visit order
     std::vector<std::vector<int>> sample_depths; // per depth of the caller's tree: indices into `sample`

@@ -76,6 +76,9 @@ struct LoopChoice {
 // best loop set of one task: every subset of the units with 2..max_iter_log2 bits (`exhaustive`), or units added
 // one at a time, cheapest first
 LoopChoice search_loops(const CostEnv &e, const std::vector<uint32_t> &ins, const std::vector<uint32_t> &outs, bool exhaustive);
+// What the cost model takes one workgroup's life for - start, staging and flush (`fix_us`), a row of the distribute pass (`iter_us`) -
+// and its streaming rate: the constants schedule() tells a bandwidth-bound level from a narrow one by (JtTask::keep_rows).
+void jtp_keep_cost(double &fix_us, double &iter_us, double &bytes_per_us);
 // Choose the F / A / R split of the high bits of a task of clique `p` and fill every index table of the task.
 int plan_loops(const HostPlan &hp, const PNode &p, JtTask &tk, std::vector<int32_t> &itab, const std::vector<MsgView> &ins,
                const std::vector<MsgView> &outs, int block_log2, std::string &err, int strict_budget = 0, double share = 1.0);

@@ -54,6 +54,10 @@ void jtp_plan_to_json(HostPlan &hp, bool with_tasks) {
       << ",\"n_messages\":" << hp.n_messages << ",\"n_tasks\":" << hp.tasks.size()
       << ",\"n_blocks\":" << hp.blocks.size() << ",\"tmix_compact\":" << (hp.tmix_compact ? 1 : 0) << ",\"lean\":" << (hp.lean ? 1 : 0) << ",\"has_unit\":" << (hp.has_unit ? 1 : 0)
       << ",\"lean_refused\":\"" << json_escape(hp.lean_refused) << "\",\"fix_doubles\":" << hp.fix_doubles << ",\"scratch_elems\":" << hp.scratch_elems << ",\"alg_bytes_full\":" << (long long)hp.alg_bytes_full;
+    o << ",\"keep\":{\"budget_bytes\":" << (long long)hp.keep_budget << ",\"collect_bytes\":" << (long long)hp.keep_bytes[0]
+      << ",\"distribute_bytes\":" << (long long)hp.keep_bytes[1] << ",\"levels\":";
+    json_vec(o, hp.keep_levels);
+    o << "}";
     o << ",\"statics\":[";
     for (size_t i = 0; i < hp.statics.size(); ++i) {
         const PStatic &st = hp.statics[i];

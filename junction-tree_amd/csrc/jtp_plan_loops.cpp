@@ -120,6 +120,13 @@ double task_cost_us(const CostEnv &e, const std::vector<uint32_t> &ins, const st
 
 }  // namespace
 
+void jtp_keep_cost(double &fix_us, double &iter_us, double &bytes_per_us) {
+    const CostK &K = cost_k();
+    fix_us = K.wg + K.stage_fix + K.flush_fix;
+    iter_us = K.iter_d;
+    bytes_per_us = K.bw;
+}
+
 LoopChoice search_loops(const CostEnv &e, const std::vector<uint32_t> &ins, const std::vector<uint32_t> &outs, bool exhaustive) {
     LoopChoice best;
     const int n = (int)e.units.size();

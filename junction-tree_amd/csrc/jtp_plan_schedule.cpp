@@ -4,23 +4,57 @@
 
 int PlanBuilder::schedule() {
     // Which passes load their table rows with the default cache policy (JtTask::keep_rows; everything else non-temporal).
-    // The levels nearest the root are read LAST by collect and FIRST by distribute: while the tables of levels 0..d (this
-    // rank's) stay below knobs.keep_rows_mb, both passes over them keep their rows in the 256 MiB Infinity Cache and the
-    // second finds them there instead of in HBM.  A plan whose tables fit altogether keeps every row (a rank's share of
-    // config 4 at 8 ranks: 152 MiB).
-    if (!hp.multiset && hp.knobs.keep_rows_mb > 0) {
+    // The levels nearest the root are read LAST by collect and FIRST by distribute: both passes over the levels chosen below (this
+    // rank's tables, knobs.keep_rows_mb in all) keep their rows in the 256 MiB Infinity Cache and the second finds them there
+    // instead of in HBM.  A plan whose tables fit the budget altogether keeps every row.  HostPlan::keep_* say what was chosen.
+    // Only where the kernels that look at the flag run - the dataflow launches of single-set plans of bit-field rows that are no
+    // chains (jt_propagate_flow, jt_propagate_flow_marg, jt_collect_flow_keep): multi-set plans, mixed-radix rows, chains and plans
+    // launched per level keep nothing, and say so (budget 0).
+    const bool keep_kernels = !hp.multiset && !hp.tmix && !hp.chain_plan && !(hp.flags & (JTP_LEVEL_LAUNCHES | JTP_SPLIT_VARIANTS)) &&
+                              !(hp.knobs.debug & 1) && !hp.knobs.force_level_launches;
+    hp.keep_budget = keep_kernels ? std::max(0.0, hp.knobs.keep_rows_mb) * 1048576.0 : 0.0;
+    hp.keep_bytes[0] = hp.keep_bytes[1] = 0;
+    hp.keep_levels.clear();
+    if (hp.keep_budget > 0) {
         std::vector<double> level_bytes(maxdepth + 1, 0.0);
+        double all_bytes = 0;
         for (int c = 0; c < NP; ++c)
-            if (mine(c) && !hp.pn[c].unit) level_bytes[hp.pn[c].depth] += (double)hp.pn[c].phys_elems * esize;
-        double cum = 0;
-        int keep_depth = -1;
-        for (int d = 0; d <= maxdepth; ++d) {
-            cum += level_bytes[d];
-            if (cum > hp.knobs.keep_rows_mb * 1048576.0) break;
-            keep_depth = d;
+            if (mine(c) && !hp.pn[c].unit) level_bytes[hp.pn[c].depth] += (double)hp.pn[c].phys_elems * esize, all_bytes += (double)hp.pn[c].phys_elems * esize;
+        std::vector<char> keep(maxdepth + 1, 0);
+        if (all_bytes <= hp.keep_budget) {
+            for (int d = 0; d <= maxdepth; ++d) keep[d] = level_bytes[d] > 0;
+        } else {
+            // By what a kept level saves.  A kept row is an HBM read the distribute pass does not make, and that is time only where the
+            // level's distribute pass is bandwidth-bound: its bytes (read + written) at the streaming rate take longer than the life
+            // of ONE of its workgroups - start, staging, its rows, flush: the level's hand-over, which no bandwidth shortens (the
+            // cost model's constants, task_cost_us).  Such levels come first, nearest the root first (the shortest time between the
+            // two passes); the narrow levels above them - a hand-over each whatever their bytes cost - take what is left.  Whole
+            // levels only: part of a level, visited by both passes in the same order, is pushed out before it is used again.
+            double fix_us, iter_us, bytes_per_us;
+            jtp_keep_cost(fix_us, iter_us, bytes_per_us);
+            if (hp.knobs.keep_bw > 0) bytes_per_us = hp.knobs.keep_bw;
+            std::vector<int> rows(maxdepth + 1, 0);              // rows per distribute workgroup, the longest of the level
+            for (const JtTask &tk : hp.tasks)
+                if (tk.kind == 0 && !tk.unit && tk.mode == 1 && mine(tk.pnode)) rows[hp.pn[tk.pnode].depth] = std::max(rows[hp.pn[tk.pnode].depth], tk.total);
+            auto bw_bound = [&](int d) { return 2.0 * level_bytes[d] / bytes_per_us > fix_us + iter_us * rows[d]; };
+            double left = hp.keep_budget;
+            int top_end = maxdepth + 1;                          // the narrow top: the levels above the first bandwidth-bound one
+            for (int d = maxdepth; d >= 0; --d)
+                if (level_bytes[d] > 0 && bw_bound(d)) top_end = d;
+            for (int pass = 0; pass < (hp.knobs.keep_top ? 2 : 1); ++pass)
+                for (int d = 0; d < (pass == 0 ? maxdepth + 1 : top_end); ++d) {
+                    if (level_bytes[d] <= 0 || keep[d] || bw_bound(d) != (pass == 0) || level_bytes[d] > left) continue;
+                    keep[d] = 1;
+                    left -= level_bytes[d];
+                }
         }
         for (JtTask &tk : hp.tasks)
-            if (tk.kind == 0 && !tk.unit && hp.pn[tk.pnode].depth <= keep_depth) tk.keep_rows = 1;
+            if (tk.kind == 0 && !tk.unit && mine(tk.pnode) && keep[hp.pn[tk.pnode].depth]) {
+                tk.keep_rows = 1;
+                if (!tk.fold) hp.keep_bytes[tk.mode ? 1 : 0] += (double)hp.pn[tk.pnode].phys_elems * esize;
+            }
+        for (int d = 0; d <= maxdepth; ++d)
+            if (keep[d]) hp.keep_levels.push_back(d);
     }
     // ---- launches, blocks, exchange schedule -----------------------------------------------------
     hp.alg_bytes = 0;

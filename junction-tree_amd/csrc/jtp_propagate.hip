@@ -72,7 +72,7 @@ struct KernelTable {
         }
         return nullptr;
     }
-    static fn get_flow(int phase, bool chain, int tmix, bool marg) {
+    static fn get_flow(int phase, bool chain, int tmix, bool marg, bool keep) {
         if (tmix == 2) return phase == 0 ? jt_collect_flow_mix<T, true> : jt_distribute_flow_mix<T, true>;
         if (tmix) return phase == 0 ? jt_collect_flow_mix<T, false> : jt_distribute_flow_mix<T, false>;      // (never merged: jtp_plan.cpp finish())
         // (marg: the plan has marginal tasks folded into its distribute phase - the build of the kernel that can run them)
@@ -81,6 +81,8 @@ struct KernelTable {
         // build of the distribute pass is the faster one (round 5, A/B by environment on one box: config 3 in two launches 8.35 -> 8.13 ms,
         // the whole gain of "one launch"; a rank's share of config 4 at 8 ranks 178 -> 176 us).  JTP_FLOW_BOTH=0: jt_distribute_flow as before.
         if (phase == 1 && !chain && flow_both()) return marg ? jt_propagate_flow_marg<T> : jt_propagate_flow<T>;
+        // (keep: the plan's collect passes keep table rows for its distribute launch - JtTask::keep_rows, the build that looks at the flag)
+        if (phase == 0 && !chain && keep) return jt_collect_flow_keep<T>;
         return phase == 0 ? jt_collect_flow<T> : (chain ? jt_distribute_flow_chain<T> : jt_distribute_flow<T>);
     }
 };
@@ -99,8 +101,8 @@ const void *kernel_fn(const HostPlan &hp, int variant) {
 }
 const void *flow_fn(const jtp_plan *pl, int phase) {
     const HostPlan &hp = pl->hp;
-    return hp.dtype == JTP_F32 ? (const void *)KernelTable<float>::get_flow(phase, pl->chain, mixk(hp), pl->marg_tasks)
-                               : (const void *)KernelTable<double>::get_flow(phase, pl->chain, mixk(hp), pl->marg_tasks);
+    return hp.dtype == JTP_F32 ? (const void *)KernelTable<float>::get_flow(phase, pl->chain, mixk(hp), pl->marg_tasks, hp.keep_bytes[0] > 0)
+                               : (const void *)KernelTable<double>::get_flow(phase, pl->chain, mixk(hp), pl->marg_tasks, hp.keep_bytes[0] > 0);
 }
 
 // dynamic LDS above 64 KiB must be allowed per kernel function: remember what each function was raised to
